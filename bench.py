@@ -223,6 +223,40 @@ def cpu_baseline(args, src, tgt, gpu_labels, gpu_eps):
     return out
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, f_src, f_tgt, h, eps, labels):
+    """--dump-outputs DIR: what the timed path handed its caller in the last timed step, one DIR/<name>.npy per array (float32 / float64),
+    so that two builds run with the same arguments can be compared output for output.  Embeddings and distance rows are a fixed, seeded
+    sample of rows (the row numbers are written beside them); labels and eps are whole.  Rank 0's view: with sharded rows, the distance
+    rows come from its own block."""
+    os.makedirs(out_dir, exist_ok=True)
+
+    def rows(n, k, seed):
+        return np.sort(np.random.default_rng(seed).choice(n, size=min(n, k), replace=False))
+
+    i_src, i_tgt = rows(f_src.shape[0], 1024, 1), rows(f_tgt.shape[0], 1024, 2)
+    i_fin = rows(h.nrows, max(1, (32 << 20) // (8 * h.N)), 3)
+    fin = h.final_dist()
+    arrays = {
+        "source_embeddings": f_src[torch.from_numpy(i_src).to(f_src.device)].float().cpu().numpy(),
+        "source_embeddings_rows": i_src.astype(np.float64),
+        "target_embeddings": f_tgt[torch.from_numpy(i_tgt).to(f_tgt.device)].float().cpu().numpy(),
+        "target_embeddings_rows": i_tgt.astype(np.float64),
+        "final_dist": fin[torch.from_numpy(i_fin).to(fin.device)].to(torch.float64).cpu().numpy(),
+        "final_dist_rows": (h.row0 + i_fin).astype(np.float64),
+        "labels": np.asarray(labels, dtype=np.float64),
+        "eps": np.array([eps], dtype=np.float64),
+    }
+    del fin
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes exceed the %d-byte budget" % (total, DUMP_BYTES))
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -247,7 +281,12 @@ def main():
                     help="time the PRODUCT DEFAULT only: no per-launch HIP events anywhere in the timed region (every embedding batch on two streams, "
                          "the re-rank's source term on its second stream on every step); the roofline objects of the line are then null -- a cross-check "
                          "of `value` against the default run, whose timed steps alternate two instrumentation modes")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (embeddings, final_dist rows: fixed seeded samples; "
+                         "labels, eps) as DIR/<name>.npy, float32 / float64, at most 64 MB")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import ssg_amd
     from ssg_amd import _lib, cluster, dist as sdist, evaluators, rerank
@@ -308,7 +347,9 @@ def main():
     src_loader = TimedLoader(src_imgs, args.batch, count=args.Ns, base=s_lo)
     imgs_rank = tgt_loader.shard(rank, world).num_items() + src_loader.shard(rank, world).num_items()
 
-    def step(group_events=True):
+    last = {}        # --dump-outputs: the last timed step's outputs (references only, nothing is copied inside the timed region)
+
+    def step(group_events=True, keep=False):
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
         ev[0].record()
         # image batches sharded by rank, C1 = all-gather of the embeddings over xGMI -- the product function
@@ -330,6 +371,8 @@ def main():
         ev[3].record()
         timer.sample = True
         os.environ.pop("SSG_RERANK_OVERLAP", None)
+        if keep:
+            last.update(f_src=f_src, f_tgt=f_tgt, h=h, eps=eps, labels=labels)
         return ev, eps, labels
 
     def sync_barrier():
@@ -345,7 +388,7 @@ def main():
     with_events = [si % 2 == 0 for si in range(args.steps)]        # steps 0, 2, 4, ..: grouping launches bracketed by events (roofline figures)
     t0 = time.perf_counter()
     for si in range(args.steps):
-        ev, eps, labels = step(with_events[si])
+        ev, eps, labels = step(with_events[si], keep=args.dump_outputs is not None and si == args.steps - 1)
         legs.append(ev)
     sync_barrier()
     elapsed = time.perf_counter() - t0
@@ -357,6 +400,9 @@ def main():
         tdist.all_reduce(t, op=tdist.ReduceOp.MAX, group=group)
         elapsed = float(t.item())
     ms_step = elapsed * 1e3 / args.steps
+    if last and rank == 0:
+        dump_outputs(args.dump_outputs, **last)
+    last.clear()
     t_embed = sum(e[0].elapsed_time(e[1]) for e in legs) / args.steps
     n_ev_steps = sum(with_events) if timer_was_on else 0
     clean = [e for e, w in zip(legs, with_events) if not (w and timer_was_on)] or legs      # (--steps 1: the one step carries the events)
