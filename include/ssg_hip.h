@@ -450,6 +450,25 @@ int ssg_triplet_grad_weights(const float* grad_dist, const float* sq, const floa
                              ssg_stream_t stream);
 int ssg_triplet_grad_combine(const float* x, const float* rowsum, const float* Sx, int n, int d, int ldo, float* grad_x, ssg_stream_t stream);
 
+/* ---- SSG++ label estimation and selection (reid/eug.py:193-290; caller semitraining.py:228-244) ------------------------
+ * ssg_eug_nn_f32: the rerank=False branch (eug.py:201-214).  For every u row: dist_j = np.linalg.norm(l - u, axis=1)[j] bit for bit
+ * (float32 differences and squares, numpy's pairwise order in sequential chunks of 8192, correctly rounded sqrt) and its np.argmin
+ * (first index on ties, first NaN wins).  u [nu,d], l [nl,d] float32 row-major, 0 < d <= 32768; nsplit = ssg_eug_nn_splits(nu, nl);
+ * part_val / part_idx: workspace of nsplit * nu entries.  Outputs (each may be NULL): argmin [nu], minval [nu] = the min distance,
+ * labels [nu] = l_label[argmin] (l_label int64 [nl], needed with labels), scores [nu] = (double)(-minval). */
+int ssg_eug_nn_splits(int nu, int nl);
+int ssg_eug_nn_f32(const float* u, int nu, const float* l, int nl, int d, const int64_t* l_label, int nsplit, float* part_val,
+                   int32_t* part_idx, int32_t* argmin, float* minval, int64_t* labels, double* scores, ssg_stream_t stream);
+/* The rerank=True branch (eug.py:228-244) on D [nu,nl] float32 (re_ranking_init's output): argmin per row (np.argmin), labels =
+ * l_label[argmin], scores = (double)(-min), confidence = (double)(1 - min / colmax[argmin]) in float32 with colmax = np.max(D, axis=0)
+ * (NaN propagates).  ws: 65 * nl floats.  argmin may be NULL. */
+int ssg_eug_dist_label_f32(const float* D, int nu, int nl, const int64_t* l_label, float* ws, int32_t* argmin, int64_t* labels,
+                           double* scores, double* confidence, ssg_stream_t stream);
+/* select_top_data (eug.py:284-289): mask[i] = 1 for the k largest of scores [n] float64 (0 <= k <= n); np.argsort(-scores) order:
+ * NaN last, -0 == +0; equal scores that straddle the cut are taken lowest index first.  labels (float64 [n] or NULL):
+ * select_top_true_data (eug.py:277-282), a selected entry whose label is -1 is cleared. */
+int ssg_eug_select_top(const double* scores, int n, int k, const double* labels, uint8_t* mask, ssg_stream_t stream);
+
 /* ---- device self-tests used by the parity suite ----------------------------------------- */
 int ssg_selftest_half_table(int which, uint16_t* out65536, ssg_stream_t stream);
 int ssg_selftest_half_binop(int which, const uint16_t* a, const uint16_t* b, int n, uint16_t* out, ssg_stream_t stream);

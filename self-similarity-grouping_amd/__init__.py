@@ -12,9 +12,15 @@ __all__ = ["re_ranking", "re_ranking_device", "DBSCAN", "eps_rule", "eps_rule_db
 
 
 def __getattr__(name):   # lazy: torch import only when the compute surface is touched
-    if name in ("re_ranking", "re_ranking_device", "re_ranking_init", "re_ranking_init_dist", "DistHandle", "ReRankNaNError"):
+    if name in ("re_ranking", "re_ranking_device", "re_ranking_init", "re_ranking_init_device", "re_ranking_init_dist", "DistHandle", "ReRankNaNError"):
         from . import rerank
         return getattr(rerank, name)
+    if name in ("estimate_label_device", "dissimilarity_from_dist", "nearest_labelled", "select_top", "EUGMixin", "updata_lable"):
+        from . import eug
+        return getattr(eug, name)
+    if name == "generate_selflabel_semi":
+        from . import semitraining
+        return semitraining.generate_selflabel
     if name in ("DBSCAN", "eps_rule", "eps_rule_dbscan", "as_handle"):
         from . import cluster
         return getattr(cluster, name)

@@ -601,9 +601,16 @@ def _init_pipeline(D, nq, k1, k2, lambda_value):
 def re_ranking_init(query_feature, gallery_feature, k1=20, k2=6, lambda_value=0.3, device=None):
     """Drop-in for reid/rerank.py:171 re_ranking_init (float32 cosine variant; numpy in, numpy
     [num_query, num_gallery] float32 out).  The stacked Gram matrix 2 - 2 x.y runs on the fp32-MFMA GEMM."""
+    q = torch.as_tensor(np.asarray(query_feature, dtype=np.float32)); g = torch.as_tensor(np.asarray(gallery_feature, dtype=np.float32))
+    return re_ranking_init_device(q, g, k1=k1, k2=k2, lambda_value=lambda_value, device=device).cpu().numpy()
+
+
+def re_ranking_init_device(query_feature, gallery_feature, k1=20, k2=6, lambda_value=0.3, device=None):
+    """re_ranking_init with the result left on the device: features as torch tensors (CPU or CUDA) or numpy arrays, returns the
+    [num_query, num_gallery] float32 CUDA tensor (the SSG++ label step, ssg_amd.eug, consumes it there)."""
     L = _lib.lib()
     device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    q = torch.as_tensor(np.asarray(query_feature, dtype=np.float32)); g = torch.as_tensor(np.asarray(gallery_feature, dtype=np.float32))
+    q = torch.as_tensor(query_feature).to(device, torch.float32); g = torch.as_tensor(gallery_feature).to(device, torch.float32)
     nq, N = q.shape[0], q.shape[0] + g.shape[0]
     x = _as_dev_f32(torch.cat([q, g], 0), device)
     npad = (-N) % 64
@@ -612,7 +619,7 @@ def re_ranking_init(query_feature, gallery_feature, k1=20, k2=6, lambda_value=0.
     Dp = torch.empty((N, N + npad), dtype=torch.float32, device=device)
     check(L.ssg_cosine_dist_f32(ptr(x), ptr(y), N, N + npad, x.shape[1], ptr(zeros), ptr(Dp), stream()), "ssg_cosine_dist_f32")
     D = Dp[:, :N].contiguous() if npad else Dp
-    return _init_pipeline(D, nq, k1, k2, lambda_value).cpu().numpy()
+    return _init_pipeline(D, nq, k1, k2, lambda_value)
 
 
 def re_ranking_init_dist(q_g_dist, q_q_dist, g_g_dist, k1=20, k2=6, lambda_value=0.3, device=None):
