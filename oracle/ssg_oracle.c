@@ -127,6 +127,21 @@ static double pairwise_sum_f64(const double* a, int64_t n) {
 }
 float ora_pairwise_sum_f32(const float* a, int64_t n) { return pairwise_sum_f32(a, n); }
 double ora_pairwise_sum_f64(const double* a, int64_t n) { return pairwise_sum_f64(a, n); }
+/* np.add.reduce on a whole contiguous array (np.sum, np.mean): the reduction runs in chunks of numpy's buffer size (8192 elements),
+ * pairwise inside each chunk, the chunk sums accumulated left to right from 0. */
+#define NUMPY_BUFSIZE 8192
+static float reduce_sum_f32(const float* a, int64_t n) {
+  float s = 0.f;
+  for (int64_t o = 0; o < n; o += NUMPY_BUFSIZE) s += pairwise_sum_f32(a + o, n - o < NUMPY_BUFSIZE ? n - o : NUMPY_BUFSIZE);
+  return s;
+}
+static double reduce_sum_f64(const double* a, int64_t n) {
+  double s = 0.;
+  for (int64_t o = 0; o < n; o += NUMPY_BUFSIZE) s += pairwise_sum_f64(a + o, n - o < NUMPY_BUFSIZE ? n - o : NUMPY_BUFSIZE);
+  return s;
+}
+float ora_reduce_sum_f32(const float* a, int64_t n) { return reduce_sum_f32(a, n); }
+double ora_reduce_sum_f64(const double* a, int64_t n) { return reduce_sum_f64(a, n); }
 
 /* scipy.spatial.distance.cdist(..., 'euclidean') inner loop (scipy/spatial/src/
  * distance_impl.h sqeuclidean_distance_double): sequential s += d*d in double. */
@@ -408,7 +423,7 @@ void ora_final(const uint16_t* J, const uint16_t* v, int N, double lambda_value,
 
 /* ------------------------------------------------------------------ selftraining.py:289-293
  * eps = mean of the round(rho*count) smallest non-zero entries of the strict upper triangle.
- * f64 matrix: np.mean = pairwise f64 sum / n.  Returns NaN when top_num == 0 (numpy mean of
+ * f64 matrix: np.mean = np.add.reduce (pairwise f64 sums of 8192-element chunks) / n.  Returns NaN when top_num == 0 (numpy mean of
  * an empty slice). count_out / top_out report the two integers. */
 static int cmp_f64(const void* a, const void* b) { double x = *(const double*)a, y = *(const double*)b; return (x > y) - (x < y); }
 double ora_eps_f64(const double* M, int N, double rho, int64_t* count_out, int64_t* top_out) {
@@ -419,11 +434,11 @@ double ora_eps_f64(const double* M, int N, double rho, int64_t* count_out, int64
   int64_t top = (int64_t)rint(rho * (double)cnt);   /* np.round: half to even */
   if (count_out) *count_out = cnt;
   if (top_out) *top_out = top;
-  double eps = top > 0 ? pairwise_sum_f64(t, top) / (double)top : NAN;
+  double eps = top > 0 ? reduce_sum_f64(t, top) / (double)top : NAN;
   free(t);
   return eps;
 }
-/* half matrix (the no-rerank euclidean_dist): np.mean(half) = float32 pairwise sum, /n in
+/* half matrix (the no-rerank euclidean_dist): np.mean(half) = float32 np.add.reduce (chunked pairwise sum), /n in
  * float64 (float32 scalar / intp scalar promotes), then np.float16(...) directly.  Returns the half bits. */
 static int cmp_h(const void* a, const void* b) { float x = h2f(*(const uint16_t*)a), y = h2f(*(const uint16_t*)b); return (x > y) - (x < y); }
 uint16_t ora_eps_f16(const uint16_t* M, int N, double rho, int64_t* count_out, int64_t* top_out) {
@@ -438,7 +453,7 @@ uint16_t ora_eps_f16(const uint16_t* M, int N, double rho, int64_t* count_out, i
   if (top > 0) {
     float* f = (float*)malloc((size_t)top * sizeof(float));
     for (int64_t i = 0; i < top; i++) f[i] = h2f(t[i]);
-    float s = pairwise_sum_f32(f, top);
+    float s = reduce_sum_f32(f, top);
     eps = d2h((double)s / (double)top);   /* np.float32 scalar / np.intp scalar -> float64, then np.float16(...) */
     free(f);
   }

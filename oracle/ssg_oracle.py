@@ -47,6 +47,8 @@ def lib():
         _lib.ora_eps_f16.restype = ctypes.c_uint16
         _lib.ora_pairwise_sum_f32.restype = ctypes.c_float
         _lib.ora_pairwise_sum_f64.restype = ctypes.c_double
+        _lib.ora_reduce_sum_f32.restype = ctypes.c_float
+        _lib.ora_reduce_sum_f64.restype = ctypes.c_double
         _lib.ora_num_threads.restype = ctypes.c_int
     return _lib
 
@@ -80,6 +82,15 @@ def pairwise_sum(a):
         return float(lib().ora_pairwise_sum_f64(_p(a, _f64p), ctypes.c_int64(a.size)))
     a = _c(a, np.float32)
     return np.float32(lib().ora_pairwise_sum_f32(_p(a, _f32p), ctypes.c_int64(a.size)))
+
+
+def reduce_sum(a):
+    """np.sum of a whole contiguous float64 / float32 array: pairwise sums of 8192-element chunks, added left to right"""
+    a = np.ascontiguousarray(a)
+    if a.dtype == np.float64:
+        return float(lib().ora_reduce_sum_f64(_p(a, _f64p), ctypes.c_int64(a.size)))
+    a = _c(a, np.float32)
+    return np.float32(lib().ora_reduce_sum_f32(_p(a, _f32p), ctypes.c_int64(a.size)))
 
 
 def argsort_half(v, small=None):

@@ -1855,10 +1855,21 @@ struct PwTree {
 
 namespace {
 struct PwLayout { int L, I, hroot; size_t o_off, o_n, o_l, o_r, o_lp, o_val, need; std::vector<char> host; };
-// numpy's pairwise-summation tree for `top` summands (depends on top only) and its packed device layout
+// numpy's summation tree for `top` summands (depends on top only) and its packed device layout.  np.add.reduce (hence np.mean) walks a
+// contiguous array in chunks of its buffer size, 8192 elements: pairwise summation inside each chunk, the chunk sums added left to
+// right -- a chain of internal nodes, one level each, on top of the chunk trees.
+constexpr long long kNumpyBufsize = 8192;
 static void pw_layout(int64_t top, PwLayout& out, bool with_tables) {
   PwTree t; std::vector<int> il, ir, ih; int hroot = 0;
-  t.build(0, top, il, ir, ih, hroot);
+  int acc = 0;
+  for (long long off = 0; off < top; off += kNumpyBufsize) {
+    int hc;
+    const int c = t.build(off, std::min<long long>(kNumpyBufsize, top - off), il, ir, ih, hc);
+    if (off == 0) { acc = c; hroot = hc; continue; }
+    hroot = (hroot > hc ? hroot : hc) + 1;
+    il.push_back(acc); ir.push_back(c); ih.push_back(hroot);
+    acc = (int)il.size() - 1;
+  }
   const int L = (int)t.leaf_off.size(), I = (int)il.size();
   out.L = L; out.I = I; out.hroot = hroot;
   // pack tables: leaf_off[L] i64 | leaf_n[L] | node_l[I] | node_r[I] | level_ptr[hroot+1] | val[(L+I)] (8 B each)
