@@ -449,6 +449,29 @@ int ssg_clamp_sqrt_f32(float* x, int64_t n, float lo, ssg_stream_t stream);
 int ssg_triplet_grad_weights(const float* grad_dist, const float* sq, const float* dist, int n, int ld, float lo, float* S, float* rowsum,
                              ssg_stream_t stream);
 int ssg_triplet_grad_combine(const float* x, const float* rowsum, const float* Sx, int n, int d, int ldo, float* grad_x, ssg_stream_t stream);
+/* The rest of that TripletLoss (reid/loss/triplet.py:32-77, csrc/triplet_loss.hip): mining, hinge, loss and prec with no host read.
+ * in [n, ld]: is_sq = 1: the squared distances of ssg_pairwise_sqdist_f32 at its row pitch, dist = sqrtf(max(sq, lo)) on the fly
+ * (bit-equal to ssg_clamp_sqrt_f32); is_sq = 0: a finished dist.  targets int64 [n] (labels); 1 <= n <= 4096; K = num_instances >= 1.
+ * semi = 1 (use_semi): anchors a = i*K + j (i < n / K), pairs (a, i*K + p) for p > j by position, an = the anchor's hardest negative,
+ * M = (n / K) * K * (K - 1) / 2; semi = 0: every row an anchor with its hardest positive (itself included) and negative, M = n.
+ * weighted = 1: the `w is not None` branch, (1/M) sum_i mean_m hinge(an_i, ap_m) (M <= 65536).
+ * rec_f: 2n + 4M floats, rec_i: 2n + 2M ints (layout in csrc/triplet_loss.hip; dist_ap = rec_f + 2n, dist_an = rec_f + 2n + M, in the
+ * reference's append order); loss, prec: one float each.  An anchor without a negative (the reference raises) makes loss and prec NaN.
+ * Up to 3 launches (mining, w-branch counts, one-workgroup fixed-order reduction). */
+int ssg_triplet_mine_f32(const float* in, int ld, int is_sq, float lo, const int64_t* targets, int n, int K, int semi, int M, float margin,
+                         int weighted, float* rec_f, int32_t* rec_i, float* loss, float* prec, ssg_stream_t stream);
+/* Backward from that record, densely: gdist [n, n] = d objective / d dist.  gloss != NULL: the objective is the loss, gloss a device
+ * pointer to its upstream gradient; else the objective is sum(gap * dist_ap) + sum(gan * dist_an) (gap / gan [M] device, may be NULL).
+ * Ties of a min / max share evenly; hinge terms >= 0 pass the gradient.  The arguments are those of the forward call. */
+int ssg_triplet_grad_dist_f32(const float* in, int ld, int is_sq, float lo, const int64_t* targets, int n, int K, int semi, int M,
+                              int weighted, const float* rec_f, const int32_t* rec_i, const float* gloss, const float* gap, const float* gan,
+                              float* gdist, ssg_stream_t stream);
+/* Feature-gradient weights straight from the record (sq at pitch ldq, the forward's is_sq = 1 input): S [n, ldS] = W + W^T,
+ * W[a,c] = sq[a,c] >= lo ? G[a,c] / dist[a,c] : 0 (diagonal 0), rowsum [n]; the same launch writes xt = x^T [dp, ldS] zero padded and
+ * zeros [dp] for the S x GEMM (ssg_conv2d_nhwc_f32), after which ssg_triplet_grad_combine forms grad_x.  ldS % 32 == 0, dp % 64 == 0. */
+int ssg_triplet_grad_weights_rec(const float* sq, int ldq, float lo, const int64_t* targets, int n, int K, int semi, int M, int weighted,
+                                 const float* rec_f, const int32_t* rec_i, const float* gloss, const float* x, int d, int ldS, int dp,
+                                 float* S, float* rowsum, float* xt, float* zeros, ssg_stream_t stream);
 
 /* ---- SSG++ label estimation and selection (reid/eug.py:193-290; caller semitraining.py:228-244) ------------------------
  * ssg_eug_nn_f32: the rerank=False branch (eug.py:201-214).  For every u row: dist_j = np.linalg.norm(l - u, axis=1)[j] bit for bit

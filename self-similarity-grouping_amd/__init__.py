@@ -46,6 +46,9 @@ def __getattr__(name):   # lazy: torch import only when the compute surface is t
     if name == "triplet_pairwise_dist":
         from . import triplet
         return triplet.pairwise_dist
+    if name == "TripletLoss":
+        from . import triplet
+        return triplet.TripletLoss
     if name in ("create", "ResNet", "synthetic_state_dict"):
         from . import resnet
         return getattr(resnet, name)
