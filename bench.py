@@ -14,8 +14,15 @@ embeddings of the same shape that are also HBM-resident; both legs are inside th
 
 Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel (the fp32-MFMA implicit
 GEMM convolution); `roofline_kernels` lists the HBM-bound distance / re-rank / DBSCAN kernels
-against their algorithmic bytes; `cpu_baseline` times the CPU oracle (a port
-of the reference algorithm) on a bounded sample on this box's host cores.
+against their algorithmic bytes.  Both come from the per-launch events of the
+timed steps.
+
+A plain run does only what the headline needs: set up, warm up, time the steps, write
+--dump-outputs, print the line.  `--full` adds the measurements that take runs of their own,
+after the timed steps: the untimed extras (other rank mode, the f32 embedding, the other
+synthetic track, the drop-in chain), the host syncs / collectives of one extra grouping leg
+(with the sparse / dense row split of `roofline_kernels`) and `cpu_baseline`, which times the
+CPU oracle (a port of the reference algorithm) on the host cores.
 """
 import argparse
 import json
@@ -257,7 +264,7 @@ def dump_outputs(out_dir, f_src, f_tgt, h, eps, labels):
         np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2)
@@ -267,13 +274,17 @@ def main():
     ap.add_argument("--batch", type=int, default=1000)     # images per embedding call (1000 x 64 x 32 x 256 x 4 B stays under the 2 GiB buffer range)
     ap.add_argument("--lambda_value", type=float, default=0.3)
     ap.add_argument("--rho", type=float, default=1.6e-3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run what the headline does not need: the untimed extras, the host-sync / collective "
+                         "count of one extra grouping leg and the CPU baseline (--no-extras / --no-cpu-baseline leave parts out)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-images", type=int, default=256)
     ap.add_argument("--cpu-n", type=int, default=0, help="grouping size of the CPU baseline (0 = the bench size, measured)")
     ap.add_argument("--track-g", choices=("hard", "separable"), default="hard",
                     help="embeddings of the timed grouping leg: 'hard' (tools/synth.hard_clustered: noise, border points, unequal identity "
-                         "sizes) or 'separable' (SURVEY 8d: 16 per identity, trivially separable); the other one is timed once, untimed-region")
-    ap.add_argument("--no-extras", action="store_true", help="skip the untimed extra measurements (f32 embed, stable rank mode, other track)")
+                         "sizes) or 'separable' (SURVEY 8d: 16 per identity, trivially separable); --full times the other one once, untimed-region")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="--full: skip the untimed extra measurements (f32 embed, stable rank mode, other track, drop-in chain)")
     ap.add_argument("--grouping", choices=("auto", "shard", "replicate"), default="auto",
                     help="N > 1: form of the grouping leg -- 'shard' (row blocks + all-gathers), 'replicate' (every rank runs the whole leg, no "
                          "collective) or 'auto' (ssg_amd.dist.choose_grouping: the form its time model predicts to be faster for this N and world size)")
@@ -284,9 +295,15 @@ def main():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step computed (embeddings, final_dist rows: fixed seeded samples; "
                          "labels, eps) as DIR/<name>.npy, float32 / float64, at most 64 MB")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    return args
+
+
+def main():
+    args = parse_args()
+    extras_on = args.full and not args.no_extras
 
     import ssg_amd
     from ssg_amd import _lib, cluster, dist as sdist, evaluators, rerank
@@ -314,7 +331,7 @@ def main():
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import synth
     gens = {"hard": synth.hard_clustered, "separable": synth.clustered}
-    emb_np = {k: (g(args.Ns, 2048, 2, intra=0.7), g(args.N, 2048, 1)) for k, g in gens.items() if k == args.track_g or not args.no_extras}
+    emb_np = {k: (g(args.Ns, 2048, 2, intra=0.7), g(args.N, 2048, 1)) for k, g in gens.items() if k == args.track_g or extras_on}
     src_emb = torch.from_numpy(emb_np[args.track_g][0]).to(dev)
     tgt_emb = torch.from_numpy(emb_np[args.track_g][1]).to(dev)
     # N > 1: the grouping leg runs in the form the product's compute_dist(..., group=, grouping='auto') would choose (VERDICT r5 #5a)
@@ -419,7 +436,7 @@ def main():
 
     # ---- untimed extras (rank 0, single GPU): what the headline configuration costs relative to its alternatives
     extras = {}
-    if world == 1 and not args.no_extras:
+    if world == 1 and extras_on:
         def timed_ms(fn, reps=2):
             fn(); torch.cuda.synchronize()
             t0 = time.perf_counter()
@@ -527,23 +544,27 @@ def main():
             "fused_path_for_comparison_s": {"embed": round(t_embed * 1e-3, 4), "rerank_eps_dbscan": round((t_rerank + t_cluster) * 1e-3, 5)}}
         del eu_np, fin_np
 
-    # host round trips and collectives of one grouping leg (re-rank + eps rule + DBSCAN), counted on an extra untimed pass -- on every
-    # rank, at any world size (the sharded path adds its own blocking reads: sizes of the ragged candidate / edge blocks)
-    with CollectiveCounter() as cc, SyncCounter() as sc:
-        h_ = rerank.re_ranking_device(src_emb, tgt_emb, k1=20, k2=6, lambda_value=args.lambda_value, keep_euclid=False, validate=False,
-                                      row0=row0, nrows=nrows, group=g_group)
-        n_rr = sc.n
-        res_ = cluster.eps_rule_dbscan(h_, args.rho, min_samples=4)
-        n_ed = sc.n - n_rr
-    row_split = cluster.sparse_row_split(h_, args.rho, res_[0]) if g_group is None else None     # which path the rows of the sparse passes took (untimed)
-    del h_
-    host_syncs = {"rerank": n_rr, "eps_rule_dbscan": n_ed, "per_split": n_rr + n_ed, "world": world,
-                  "what": "blocking device->host reads (item/tolist/cpu) of one grouping leg on rank 0: value ranges of the features (re-rank); ONE read for "
-                          "eps rule + DBSCAN on one GPU (labels, neighbour counts, eps, check words, the re-rank's status words -- cluster.eps_rule_dbscan); "
-                          "sharded rows (round 6) run the same chain with two all-gathers inside and the same ONE read (labels + counts + check words + every rank's status words); a failed check falls back to the two-call form"}
-    collectives = cc.summary()
-    collectives["what"] = ("torch.distributed collectives of one grouping leg on rank 0 (all-gathers of the row-block tables: source minima, rank lists, V, V_qe, "
-                           "eps candidates, neighbour counts, edges; all-reduces of the eps histograms / counters); bytes = this rank's contribution / what it receives")
+    # --full: host round trips and collectives of one grouping leg (re-rank + eps rule + DBSCAN), counted on an extra untimed pass -- on
+    # every rank, at any world size (the sharded path adds its own blocking reads: sizes of the ragged candidate / edge blocks)
+    counted, row_split = {}, None
+    if args.full:
+        with CollectiveCounter() as cc, SyncCounter() as sc:
+            h_ = rerank.re_ranking_device(src_emb, tgt_emb, k1=20, k2=6, lambda_value=args.lambda_value, keep_euclid=False, validate=False,
+                                          row0=row0, nrows=nrows, group=g_group)
+            n_rr = sc.n
+            res_ = cluster.eps_rule_dbscan(h_, args.rho, min_samples=4)
+            n_ed = sc.n - n_rr
+        row_split = cluster.sparse_row_split(h_, args.rho, res_[0]) if g_group is None else None     # which path the rows of the sparse passes took (untimed)
+        del h_
+        counted["host_syncs"] = {
+            "rerank": n_rr, "eps_rule_dbscan": n_ed, "per_split": n_rr + n_ed, "world": world,
+            "what": "blocking device->host reads (item/tolist/cpu) of one grouping leg on rank 0: value ranges of the features (re-rank); ONE read for "
+                    "eps rule + DBSCAN on one GPU (labels, neighbour counts, eps, check words, the re-rank's status words -- cluster.eps_rule_dbscan); "
+                    "sharded rows (round 6) run the same chain with two all-gathers inside and the same ONE read (labels + counts + check words + every rank's status words); a failed check falls back to the two-call form"}
+        counted["collectives"] = cc.summary()
+        counted["collectives"]["what"] = (
+            "torch.distributed collectives of one grouping leg on rank 0 (all-gathers of the row-block tables: source minima, rank lists, V, V_qe, "
+            "eps candidates, neighbour counts, edges; all-reduces of the eps histograms / counters); bytes = this rank's contribution / what it receives")
     if rank != 0:
         return
     n_img = args.N + args.Ns
@@ -621,7 +642,7 @@ def main():
         "grouping_timing": grouping_timing,
         "labels": {"clusters": int(labels.max() + 1), "noise": int((labels < 0).sum()), "eps": eps,
                    "sha256": __import__("hashlib").sha256(np.ascontiguousarray(labels, dtype=np.int64).tobytes()).hexdigest()[:16]},
-        "rank_mode": rerank.default_rank_mode(), "host_syncs": host_syncs, "collectives": collectives, "build": build_fingerprint(),
+        "rank_mode": rerank.default_rank_mode(), **counted, "build": build_fingerprint(),
         "roofline": roof, "roofline_kernels": hbm,
         "roofline_k5_k12": k5_k12,
     }
@@ -629,7 +650,7 @@ def main():
     if "rank_mode" in extras and "ssg_topk_rank_introsort" in tot and hbm_ms is not None:
         alt_ms = hbm_ms - tot["ssg_topk_rank_introsort"][1] / max(n_ev_steps, 1) + extras["rank_mode"]["stable_kernel_ms"]
         out["roofline_k5_k12"]["frac_with_stable_order"] = round(8.0 * nrows * args.N / (alt_ms * 1e-3) / 1e9 / PEAK_HBM_GBS, 4)
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         _lib._lib = timer.L
         out["cpu_baseline"] = cpu_baseline(args, emb_np[args.track_g][0], emb_np[args.track_g][1], labels, eps)
     print(json.dumps(out))

@@ -507,13 +507,15 @@ def test_config4_sharded_footprint_and_result():
         min(x[4] for x in res) / 1e9, max(x[4] for x in res) / 1e9, 2 * block / 1e9))
 
 
-def _run_bench(world, extra_env=None, extra_args=()):
-    """bench.py as the driver launches it (torchrun for world > 1), on a reduced problem; returns the parsed JSON line"""
+def _run_bench(world, extra_env=None, extra_args=(), full=True):
+    """bench.py as the driver launches it (torchrun for world > 1), on a reduced problem; returns the parsed JSON line.
+    full: --full without the extras and the CPU baseline (the line then carries host_syncs / collectives); else a plain run"""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    args = ["--gpus", str(world), "--steps", "1", "--warmup", "0", "--N", "4000", "--Ns", "2000", "--batch", "250", "--no-cpu-baseline", "--no-extras"]
+    args = ["--gpus", str(world), "--steps", "1", "--warmup", "0", "--N", "4000", "--Ns", "2000", "--batch", "250"]
+    args += ["--full", "--no-cpu-baseline", "--no-extras"] if full else []
     args += list(extra_args)
     env = dict(os.environ, OMP_NUM_THREADS="8", MKL_NUM_THREADS="8", HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.update(extra_env or {})
@@ -556,3 +558,19 @@ def test_bench_step_at_world_2_and_8_equals_world_1():
     auto = _run_bench(2, {"SSG_BENCH_SHARE_GPU": "1"})
     assert auto["config"]["grouping_form"] == "replicate" and auto["collectives"]["n"] == 0, (auto["config"]["grouping_form"], auto["collectives"])
     assert auto["labels"] == one["labels"]
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_headline_only():
+    """bench.py without --full does only what its headline needs: no extra grouping leg (host_syncs / collectives), no untimed extras and
+    no CPU baseline even though neither is switched off; the headline fields and the timed steps' labels are those of a --full run."""
+    plain = _run_bench(1, full=False)
+    full = _run_bench(1)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "labels", "roofline", "roofline_kernels"):
+        assert k in plain, k
+    moved = {"host_syncs", "collectives", "cpu_baseline", "embed_precision_f32", "grouping_other_track", "dropin_chain"}
+    assert not moved & set(plain), sorted(moved & set(plain))
+    assert isinstance(plain["rank_mode"], str)
+    assert {"host_syncs", "collectives"} <= set(full)
+    assert {k: plain[k] for k in ("metric", "unit", "higher_is_better", "dtype")} == {k: full[k] for k in ("metric", "unit", "higher_is_better", "dtype")}
+    assert plain["labels"] == full["labels"]

@@ -318,3 +318,17 @@ def test_bench_quotes_pmc_traffic_only_for_its_own_build(tmp_path):
     if os.path.exists(bench.PMC_TRAFFIC_JSON):
         assert json.load(open(bench.PMC_TRAFFIC_JSON))["embed_build"] == bench.embed_fingerprint(), \
             "%s is stale: re-run tools/pmc_embed.sh on the GPU box" % bench.PMC_TRAFFIC_JSON
+
+
+def test_bench_full_is_opt_in():
+    """bench.py --gpus 1 --steps K --warmup W is the plain run (headline only); what takes runs of its own needs --full"""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("ssg_bench", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    plain = bench.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert (plain.gpus, plain.steps, plain.warmup, plain.full, plain.dump_outputs) == (1, 3, 1, False, None)
+    full = bench.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"])
+    assert full.full and full.no_cpu_baseline and not full.no_extras
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])

@@ -5,7 +5,7 @@ set -x
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/r03; mkdir -p $O
 cd $R
-python bench.py --steps 2 --warmup 1 > $O/bench_final.json 2> $O/bench_final.err; tail -2 $O/bench_final.err
+python bench.py --full --steps 2 --warmup 1 > $O/bench_final.json 2> $O/bench_final.err; tail -2 $O/bench_final.err
 python tools/layer_table.py > $O/layer_table.md 2>&1
 python tools/run_configs.py 0 1 2 3 4 > $O/configs.jsonl 2> $O/configs.err; cut -c1-300 $O/configs.jsonl
 cd /tmp && export TMPDIR=/tmp

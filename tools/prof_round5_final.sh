@@ -10,7 +10,7 @@ cd $R
 PARTS=${PARTS:-"pmc bench prof2 prof1 layer configs pmcgroup"}
 has() { [[ " $PARTS " == *" $1 "* ]]; }
 if has pmc; then PMC_PREFIX=r05 timeout 900 bash tools/pmc_embed.sh > $O/pmc_embed.log 2>&1; tail -2 $O/pmc_embed.log; cp $R/gpurun_out/r05_pmc_conv_traffic.json $R/gpurun_out/r05_pmc_conv_traffic.md $R/profiles/; fi
-if has bench; then timeout 1200 python bench.py --steps 5 --warmup 2 > $O/bench_final.json 2> $O/bench_final.err; tail -2 $O/bench_final.err; cut -c1-300 $O/bench_final.json; fi
+if has bench; then timeout 1200 python bench.py --full --steps 5 --warmup 2 > $O/bench_final.json 2> $O/bench_final.err; tail -2 $O/bench_final.err; cut -c1-300 $O/bench_final.json; fi
 cd /tmp && export TMPDIR=/tmp
 if has prof2; then
   timeout 900 rocprofv3 --kernel-trace --stats -d $O/prof2 -o bench -- python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extras > $O/bench_under_rocprof_two_streams.json 2> $O/prof2_err.log

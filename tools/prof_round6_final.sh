@@ -16,7 +16,7 @@ PARTS=${PARTS:-"pmc bench prof1 prof2 layer configs pmcchain micro"}
 has() { [[ " $PARTS " == *" $1 "* ]]; }
 if has pmc; then PMC_PREFIX=r06 timeout 900 bash tools/pmc_embed.sh > $O/pmc_embed.log 2>&1; tail -2 $O/pmc_embed.log; cp $R/gpurun_out/r06_pmc_conv_traffic.json $R/gpurun_out/r06_pmc_conv_traffic.md $R/profiles/; fi
 if has bench; then
-  timeout 1200 python bench.py --steps 5 --warmup 2 > $O/bench_final.json 2> $O/bench_final.err; tail -2 $O/bench_final.err; cut -c1-300 $O/bench_final.json
+  timeout 1200 python bench.py --full --steps 5 --warmup 2 > $O/bench_final.json 2> $O/bench_final.err; tail -2 $O/bench_final.err; cut -c1-300 $O/bench_final.json
   timeout 600 python bench.py --steps 5 --warmup 2 --uniform --no-cpu-baseline --no-extras > $O/bench_uniform.json 2> $O/bench_uniform.err; cut -c1-200 $O/bench_uniform.json
 fi
 cd /tmp && export TMPDIR=/tmp
