@@ -439,6 +439,18 @@ int ssg_jpeg_parse_open(const void* const* files, const int64_t* lens, int nfile
 int ssg_jpeg_parse_fill(void* handle, int64_t* imgs, int64_t* segs, uint8_t* pool, uint16_t* look, int32_t* maxcode, int32_t* valoff,
                         uint8_t* vals, uint16_t* qts);
 int ssg_jpeg_parse_close(void* handle);
+/* ---- training transform of the fine-tune loader (ssg_amd/trainloader.py; the per-item transform of selftraining.py:177-183 and
+ * reid/eug.py:64-71): for every image b of a batch of ANY mix of source sizes, in one launch,
+ *   out[b] = Normalize(ToTensor(flip(PIL.Image.crop(box).resize((W, H), BILINEAR)))) with the erase rectangle set to float32(fill[c]),
+ * bit-exact with Pillow 12.2 + the published float32 formulas.  desc: device int32 [B, SSG_TT_WORDS = 20], per image:
+ *   0-1 source address (uint8 [h, w, 3] RGB, low / high word), 2 h, 3 w, 4-7 crop box x0, y0, cw, ch,
+ *   8 x-window offset into coef, 9 its ksize, 10 y-window offset, 11 its ksize, 12 flip (0 / 1),
+ *   13-16 erase rectangle: first row, first column, rows eh, columns ew (eh = 0: none), 17-19 unused.
+ * coef: device int32, per axis block at its offset: first[n], count[n], k[n, ksize] (n = W for x, H for y, Pillow's windows of the crop
+ * size -> n; first relative to the crop).  One workgroup per (image, band of band_rows output rows); lds_rows >= the crop rows any band's
+ * vertical windows read (lds_rows * W * 3 <= 65536).  mean3 / std3 / fill3: HOST pointers to 3 floats.  out [B, 3, H, W] float32. */
+int ssg_train_transform_u8(const int32_t* desc, int B, const int32_t* coef, int H, int W, int band_rows, int lds_rows, const float* mean3_host,
+                           const float* std3_host, const float* fill3_host, float* out, ssg_stream_t stream);
 /* x = sqrt(max(x, lo)) in place: with ssg_pairwise_sqdist_f32 the pairwise block of the fine-tune phase's TripletLoss
  * (reid/loss/triplet.py:28-31: dist = (|x|^2 + |x|^2' - 2 x x').clamp(min=1e-12).sqrt()) */
 int ssg_clamp_sqrt_f32(float* x, int64_t n, float lo, ssg_stream_t stream);

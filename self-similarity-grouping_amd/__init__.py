@@ -49,6 +49,9 @@ def __getattr__(name):   # lazy: torch import only when the compute surface is t
     if name == "TripletLoss":
         from . import triplet
         return triplet.TripletLoss
+    if name in ("GpuTrainLoader", "TrainTransform", "generate_dataloader"):
+        from . import trainloader
+        return getattr(trainloader, name)
     if name in ("create", "ResNet", "synthetic_state_dict"):
         from . import resnet
         return getattr(resnet, name)

@@ -169,6 +169,23 @@ class EUGMixin(object):
         return generate_new_train_data(self.l_data, self.u_data, self.u_label, sel_idx, pred_y)
 
 
+class EUGTrainLoaderMixin(object):
+    """Opt-in override of reid/eug.py:62-96 get_dataloader (class EUG(EUGTrainLoaderMixin, EUGMixin, EUG): pass): the training loader of
+    the num_classes == 0 branch -- RandomSizedRectCrop, RandomHorizontalFlip, ToTensor, Normalize, RandomErasing(0.5, sh=0.2, r1=0.3) with
+    RandomIdentitySampler(dataset, num_instances), drop_last -- is an ssg_amd.trainloader.GpuTrainLoader with the same random streams;
+    every other loader is the base class's."""
+
+    def get_dataloader(self, dataset, training=False):
+        if not (training and self.num_classes == 0):
+            return super(EUGTrainLoaderMixin, self).get_dataloader(dataset, training=training)
+        from .trainloader import GpuTrainLoader, TrainTransform
+        tf = TrainTransform(self.data_height, self.data_width, crop="random_rect", flip_p=0.5, mean=(0.485, 0.456, 0.406),
+                            std=(0.229, 0.224, 0.225), erase_p=0.5, sh=0.2, r1=0.3)
+        print("create dataloader for Training with batch_size {}".format(self.batch_size))
+        return GpuTrainLoader(dataset, root=None, transform=tf, batch_size=self.batch_size, num_instances=self.num_instances,
+                              num_workers=self.data_workers)
+
+
 def generate_new_train_data(l_data, u_data, u_label, sel_idx, pred_y):
     """eug.py:292-310: the labelled list followed by [fname, int(predicted label), camid] of every selected unlabelled image."""
     selected = []
