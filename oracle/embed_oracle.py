@@ -1,4 +1,4 @@
-"""Plain PyTorch fp32 CPU restatement of the embedding path (TEST INFRASTRUCTURE ONLY).
+"""Plain PyTorch CPU restatement of the embedding path, fp32 or fp64 (TEST INFRASTRUCTURE ONLY).
 
 Floating-point kernels keep a torch fp32 reference (the task's rule for fp kernels); this
 restates, with torch.nn.functional on the CPU:
@@ -8,6 +8,10 @@ restates, with torch.nn.functional on the CPU:
 from a state_dict with the reference's key names.  It is pinned against the real reference
 model (run with stub torchvision/h5py/metric_learn modules) by tools/make_golden.py ->
 tests/golden/embed_ref.npz.
+
+`dtype=torch.float64` runs the same statements in double precision: the reference the kernel tests measure BOTH the HIP path
+and the fp32 restatement against.  `stem` / `bottleneck` restate one fused launch each (csrc/stem_pool.hip,
+csrc/bottleneck.hip) from the raw convolution weights and BatchNorm tensors, NCHW, in the dtype of their input.
 """
 import torch
 import torch.nn.functional as F
@@ -19,8 +23,37 @@ def _bn(x, sd, name):
     return F.batch_norm(x, sd[name + ".running_mean"], sd[name + ".running_var"], sd[name + ".weight"], sd[name + ".bias"], False, 0.0, 1e-5)
 
 
-def feature_map(sd, x):
-    """x [B,3,H,W] float32 -> layer4 output [B,2048,H/32,W/32] (resnet.py:87-92)."""
+def _bn_t(x, bn):
+    """eval BatchNorm from (weight, bias, running_mean, running_var); a single 1-D tensor instead is the bias of a convolution
+    whose weights already carry the folded BatchNorm scale (what the kernels are given)"""
+    if torch.is_tensor(bn):
+        return x + bn.to(x.dtype).view(1, -1, 1, 1)
+    g, b, m, v = (t.to(x.dtype) for t in bn)
+    return F.batch_norm(x, m, v, g, b, False, 0.0, 1e-5)
+
+
+def stem(x, w, bn, flip=False):
+    """x [B,3,H,W] -> conv 7x7 s2 p3 -> eval BN -> ReLU -> maxpool 3x3 s2 p1 (base.py:101-105), of fliplr(x) when flip."""
+    if flip:
+        x = fliplr(x)
+    return F.max_pool2d(F.relu(_bn_t(F.conv2d(x, w.to(x.dtype), None, 2, 3), bn)), 3, 2, 1)
+
+
+def bottleneck(x, convs, bns, downsample=None):
+    """the stride-1 Bottleneck (base.py:57-90): convs = (w1 1x1, w2 3x3, w3 1x1), bns = their BatchNorm 4-tuples,
+    (or folded biases, see _bn_t), downsample = (w 1x1, bn) or None (identity shortcut)."""
+    out = F.relu(_bn_t(F.conv2d(x, convs[0].to(x.dtype)), bns[0]))
+    out = F.relu(_bn_t(F.conv2d(out, convs[1].to(x.dtype), None, 1, 1), bns[1]))
+    out = _bn_t(F.conv2d(out, convs[2].to(x.dtype)), bns[2])
+    res = x if downsample is None else _bn_t(F.conv2d(x, downsample[0].to(x.dtype)), downsample[1])
+    return F.relu(out + res)
+
+
+def feature_map(sd, x, dtype=None):
+    """x [B,3,H,W] -> layer4 output [B,2048,H/32,W/32] (resnet.py:87-92); dtype: cast x and the weights first."""
+    if dtype is not None:
+        sd = {k: v.to(dtype) for k, v in sd.items() if v.dtype.is_floating_point}
+        x = x.to(dtype)
     x = F.relu(_bn(F.conv2d(x, sd["base.conv1.weight"], None, 2, 3), sd, "base.bn1"))
     x = F.max_pool2d(x, 3, 2, 1)
     for li, n in enumerate(_LAYERS):
@@ -53,9 +86,10 @@ def fliplr(img):
     return img.index_select(3, torch.arange(img.size(3) - 1, -1, -1).long())
 
 
-def embed_with_flip(sd, imgs, num_split):
-    """evaluators.py:28-35: per set (a + b) / ||a + b||."""
-    sd = {k: v.float() for k, v in sd.items() if v.dtype.is_floating_point}
+def embed_with_flip(sd, imgs, num_split, dtype=torch.float32):
+    """evaluators.py:28-35: per set (a + b) / ||a + b||, computed and returned in `dtype`."""
+    sd = {k: v.to(dtype) for k, v in sd.items() if v.dtype.is_floating_point}
+    imgs = imgs.to(dtype)
     with torch.no_grad():
         a = pooled(feature_map(sd, imgs), num_split)
         b = pooled(feature_map(sd, fliplr(imgs)), num_split)

@@ -25,7 +25,8 @@ class SSGError(RuntimeError):
 
 def parse_header(path=HEADER):
     """-> {name: (restype, [argtypes])} for every prototype in the header."""
-    text = open(path).read()
+    with open(path) as f:
+        text = f.read()
     text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
     text = re.sub(r"^\s*#.*$", " ", text, flags=re.M)
     protos = {}
