@@ -354,7 +354,7 @@ int ssg_nchw_to_nhwc4(const float* in, float* out, int B, int H, int W, int flip
 int ssg_maxpool3x3s2_nhwc(const float* in, float* out, int B, int H, int W, int C, ssg_stream_t stream);
 /* out[s][b][c]: s=0 global average pool, s=1..S the S horizontal stripes (resnet.py:93-111) */
 int ssg_gap_stripes(const float* in, float* out, int B, int H, int W, int C, int num_split, ssg_stream_t stream);
-/* out = (a+b)/||a+b||_2 per row (evaluators.py:31-35: original + flipped features, L2 norm) */
+/* out = (a+b)/||a+b||_2 per row (evaluators.py:31-35: original + flipped features, L2 norm); out may alias neither a nor b */
 int ssg_flip_sum_l2norm(const float* a, const float* b, float* out, int rows, int C, ssg_stream_t stream);
 
 /* ---- kNN-set Jaccard re-ranking variant (reid/rerank_plain.py:125-178 re_ranking; shares K3/K4 with rerank.py) */

@@ -4,7 +4,8 @@ Floating-point kernels keep a torch fp32 reference (the task's rule for fp kerne
 restates, with torch.nn.functional on the CPU:
   reid/models/base.py:57-93,96-152   Bottleneck ResNet-50 (conv / eval BatchNorm / ReLU / maxpool)
   reid/models/resnet.py:86-111       stop before avgpool; global + stripe average pooling
-  reid/evaluators.py:12-16,28-35     fliplr, sum of both orientations, per-set L2 normalisation
+  reid/models/resnet.py:112-124      x2 = relu(feat_bn(feat(x1[0]))); for_eval: the sets concatenated
+  reid/evaluators.py:12-16,28-35     fliplr, sum of both orientations, L2 normalisation (per set, or of the concatenation)
 from a state_dict with the reference's key names.  It is pinned against the real reference
 model (run with stub torchvision/h5py/metric_learn modules) by tools/make_golden.py ->
 tests/golden/embed_ref.npz.
@@ -86,17 +87,38 @@ def fliplr(img):
     return img.index_select(3, torch.arange(img.size(3) - 1, -1, -1).long())
 
 
-def embed_with_flip(sd, imgs, num_split, dtype=torch.float32):
-    """evaluators.py:28-35: per set (a + b) / ||a + b||, computed and returned in `dtype`."""
+def heads(sd, fmap, num_split, for_eval=False):
+    """resnet.py:93-124 from the layer4 map on (num_classes = 0, eval mode), in the dtype of fmap and sd: -> (x1, x2).
+    x1 = the un-normalised pooled sets (a list of S+1 [B,2048], their concatenation [B,(S+1)*2048] when for_eval, a single
+    [B,2048] when num_split <= 1); x2 = relu(feat_bn(feat(global average)))."""
+    x1 = pooled(fmap, num_split)
+    x2 = None
+    if "feat.weight" in sd:          # num_features > 0
+        x2 = F.relu(_bn(F.linear(x1[0] if num_split > 1 else x1, sd["feat.weight"]), sd, "feat_bn"))
+    if num_split > 1 and for_eval:
+        x1 = torch.cat(x1, dim=1)
+    return x1, x2
+
+
+def forward(sd, x, num_split, for_eval=False, dtype=torch.float32):
+    """resnet.py:86-124: model(x, for_eval) -> (x1, x2), computed and returned in `dtype`."""
     sd = {k: v.to(dtype) for k, v in sd.items() if v.dtype.is_floating_point}
-    imgs = imgs.to(dtype)
     with torch.no_grad():
-        a = pooled(feature_map(sd, imgs), num_split)
-        b = pooled(feature_map(sd, fliplr(imgs)), num_split)
-        if not isinstance(a, list):
-            a, b = [a], [b]
-        out = []
-        for x, y in zip(a, b):
-            s = x + y
-            out.append(s / torch.norm(s, p=2, dim=1, keepdim=True))
-    return out
+        return heads(sd, feature_map(sd, x.to(dtype)), num_split, for_eval)
+
+
+def sum_norm(a, b):
+    """evaluators.py:31-35 / 41-43 on one feature set: (a + b) / ||a + b|| per row."""
+    s = a + b
+    return s / torch.norm(s, p=2, dim=1, keepdim=True)
+
+
+def embed_with_flip(sd, imgs, num_split, dtype=torch.float32, for_eval=False):
+    """evaluators.py:28-35: per set (a + b) / ||a + b||, computed and returned in `dtype` (a list of S+1 [B,2048]);
+    for_eval (evaluators.py:40-43): the model hands over the concatenated sets, so ONE norm over all (S+1)*2048 columns
+    -> [B,(S+1)*2048] (a single set, num_split <= 1, comes back as a list of one either way)."""
+    a = forward(sd, imgs, num_split, for_eval, dtype)[0]
+    b = forward(sd, fliplr(imgs), num_split, for_eval, dtype)[0]
+    if isinstance(a, list):
+        return [sum_norm(x, y) for x, y in zip(a, b)]
+    return sum_norm(a, b) if (for_eval and num_split > 1) else [sum_norm(a, b)]

@@ -460,6 +460,8 @@ class ResNet:
         L = _lib.lib()
         B, h, w, C = fmap.shape
         S = self.num_split if self.num_split > 1 else 1
+        if S > h:       # the reference slices h // num_split = 0 rows per stripe and fails inside avg_pool2d (resnet.py:99-107)
+            raise _lib.SSGError("num_split = %d stripes on a layer4 map of %d rows (input height too small): no such feature" % (S, h))
         nsets = S + 1 if S > 1 else 1
         out = torch.empty((nsets, B, C), dtype=torch.float32, device=fmap.device)
         if split:

@@ -159,3 +159,36 @@ def test_comm_entry_points_world1_on_rccl():
     assert torch.equal(comm.all_reduce_sum_(hh.clone()), hh)
     torch.cuda.synchronize()
     comm.destroy()
+
+
+# Entry points that no file under tests/ names: they are reached only through the Python wrappers (ssg_amd/*.py), never with arguments a
+# test chose.  Frozen when the check below was added; written without the ssg_ prefix so that this list does not itself count as a
+# mention.  The list may only SHRINK: an entry point leaves it when a test calls it by name, and a new export must arrive with such a test.
+_ONLY_THROUGH_WRAPPERS = """
+affine_2m2x_f32 clamp_sqrt_f32 concat_segments_u64 cosine_dist_f32 dbscan_cc_dev dbscan_cc_workspace_bytes eps_compact eps_mean fill_u64
+half_min invert_index jaccard_rows jaccard_segments jpeg_decode_batch jpeg_parse_close jpeg_parse_fill pairwise_sqdist_f32 query_expand
+rank_metrics_all region_query_dev region_query_s_dev rerank_init_expand rerank_init_jaccard rerank_init_stage1 row_norms_f64
+samplesort_u64_presplit_dev source_rowmin_f16 source_rowmin_filtered1 topk_rank_introsort_arena_bytes topk_rank_introsort_flags_offset
+topk_rank_introsort_ws_bytes triplet_grad_combine triplet_grad_weights
+""".split()
+
+
+def test_every_exported_entry_point_is_named_in_a_test():
+    """every ssg_* function of include/ssg_hip.h is called by name in at least one file under tests/, or stands on the frozen list above"""
+    import re
+    here = os.path.dirname(os.path.abspath(__file__))
+    text = "\n".join(open(os.path.join(here, f)).read() for f in sorted(os.listdir(here)) if f.endswith(".py"))
+    declared = sorted(_lib.parse_header())
+    unnamed = [n for n in declared if not re.search(r"\b%s\b" % n, text)]
+    listed = ["ssg_" + n for n in _ONLY_THROUGH_WRAPPERS]
+    assert len(listed) == len(set(listed)) <= 33, "the list may only shrink"
+    assert not [n for n in listed if n not in declared], "the list names something the header does not declare"
+    new = [n for n in unnamed if n not in listed]
+    assert not new, "exported without a test that calls them by name: %r" % new
+    stale = [n for n in listed if n not in unnamed]
+    assert not stale, "now named in a test: take them off the list: %r" % stale
+    # the embedder's layout / pooling / normalisation kernels and the split-half pair have tests of their own (tests/test_gpu_embed_layers.py)
+    for n in ("ssg_nchw_to_nhwc4", "ssg_nchw_to_nhwc4_h4l4", "ssg_maxpool3x3s2_nhwc", "ssg_maxpool3x3s2_h8l8", "ssg_gap_stripes", "ssg_gap_stripes_h8l8",
+              "ssg_flip_sum_l2norm", "ssg_conv1x1_dual_nhwc_f32", "ssg_h8l8_encode", "ssg_h8l8_decode"):
+        assert n in declared and n not in listed
+        assert re.search(r"\bL\.%s\b" % n, open(os.path.join(here, "test_gpu_embed_layers.py")).read()), n

@@ -1,6 +1,7 @@
 """CPU suite: the torch-fp32 restatement of the embedding path against the golden features
 produced by the real reference model (tools/make_golden.py, tests/golden/embed_ref.npz)."""
 import numpy as np
+import pytest
 import torch
 
 
@@ -111,3 +112,65 @@ def test_block_restatements_are_the_feature_maps_own_statements():
         r = embed_oracle._bn(torch.nn.functional.conv2d(z, sd[p + ".downsample.0.weight"]), sd, p + ".downsample.1") if b == 0 else z
         z = torch.relu(o + r)
     assert torch.equal(y, z)
+
+
+def _randomised_feat_bn(sd, seed=0):
+    """feat_bn statistics away from the identity (as test_x2_branch_matches_torch draws them), so that x2 checks the folding"""
+    g = torch.Generator().manual_seed(seed)
+    sd = dict(sd)
+    sd["feat_bn.running_mean"] = torch.randn(2048, generator=g) * 0.01; sd["feat_bn.running_var"] = torch.rand(2048, generator=g) + 0.5
+    sd["feat_bn.weight"] = torch.rand(2048, generator=g) + 0.5; sd["feat_bn.bias"] = torch.randn(2048, generator=g) * 0.01
+    return sd
+
+
+def test_forward_and_joint_norm_restatements_match_the_golden_and_each_other(golden):
+    """embed_oracle.forward (resnet.py:86-124: the un-normalised sets x1 and x2) and embed_with_flip(for_eval=True) (evaluators.py:40-43:
+    one norm over the concatenated sets) are what tests/test_gpu_embed_outputs.py judges the HIP model's un-normalised and jointly
+    normalised outputs by.  Pinned here: the golden per-set features re-derived from forward's un-normalised sets; the joint form
+    against the same sets by hand and against the golden up to the per-image factors it must differ by; x2 against the plain
+    formula; float32 against float64."""
+    import ssg_amd
+    from oracle import embed_oracle as eo
+    g = golden("embed_ref.npz")
+    sd = _randomised_feat_bn(ssg_amd.synthetic_state_dict(seed=int(g["weight_seed"])))
+    imgs = torch.randn(4, 3, 256, 128, generator=torch.Generator().manual_seed(int(g["image_seed"])))[:2]
+    ref = torch.from_numpy(g["feats_S2"][:, :2]).double()
+    out = {}
+    for dt in (torch.float64, torch.float32):
+        x1, x2 = eo.forward(sd, imgs, 2, False, dt)
+        y1, _ = eo.forward(sd, eo.fliplr(imgs), 2, False, dt)
+        assert isinstance(x1, list) and len(x1) == 3 and all(t.shape == (2, 2048) and t.dtype == dt for t in x1) and x2.shape == (2, 2048) and x2.dtype == dt
+        cat, x2e = eo.forward(sd, imgs, 2, True, dt)
+        assert torch.equal(cat, torch.cat(x1, 1)) and torch.equal(x2e, x2)              # for_eval only concatenates
+        # the golden features are these sets, summed over both orientations and normalised per set
+        mine = torch.stack([eo.sum_norm(a, b) for a, b in zip(x1, y1)])
+        assert float((mine.double() - ref).abs().max()) < 5e-6
+        assert torch.equal(mine, torch.stack(eo.embed_with_flip(sd, imgs, 2, dt)))
+        # the joint form: one norm over the 3 * 2048 columns
+        joint = eo.embed_with_flip(sd, imgs, 2, dt, for_eval=True)
+        s = torch.cat(x1, 1) + torch.cat(y1, 1)
+        assert joint.shape == (2, 6144) and torch.equal(joint, s / s.norm(dim=1, keepdim=True))
+        tol = 1e-12 if dt == torch.float64 else 1e-5
+        assert float((joint.double().norm(dim=1) - 1).abs().max()) < tol
+        # ... which is the per-set golden with set s scaled by ||a_s + b_s|| / ||all sets||: a ratio the per-set form divides out
+        w = torch.stack([(a + b).double().norm(dim=1) for a, b in zip(x1, y1)])                                   # [3, 2]
+        w = w / w.pow(2).sum(0).sqrt()
+        assert float((joint.double().view(2, 3, 2048).permute(1, 0, 2) - ref * w.unsqueeze(2)).abs().max()) < 5e-6
+        assert float(w.max() / w.min()) > 1.001         # the sets do differ in norm: the ratio is information
+        # x2 = relu(feat_bn(feat(x1[0]))), resnet.py:112-117
+        z = x1[0].double() @ sd["feat.weight"].double().t()
+        z = (z - sd["feat_bn.running_mean"].double()) / torch.sqrt(sd["feat_bn.running_var"].double() + 1e-5) * sd["feat_bn.weight"].double() + sd["feat_bn.bias"].double()
+        assert float((x2.double() - torch.relu(z)).abs().max()) < (1e-12 if dt == torch.float64 else 2e-6) * max(1.0, float(z.abs().max()))
+        assert float((x2 > 0).float().mean()) > 0.2
+        # one set: a tensor, not a list; heads() on a map is forward()
+        p1, q2 = eo.forward(sd, imgs, 1, False, dt)
+        assert torch.is_tensor(p1) and torch.equal(p1, x1[0]) and torch.equal(q2, x2)
+        sdd = {k: v.to(dt) for k, v in sd.items() if v.dtype.is_floating_point}
+        h1, h2 = eo.heads(sdd, eo.feature_map(sdd, imgs.to(dt)), 2)
+        assert all(torch.equal(a, b) for a, b in zip(h1, x1)) and torch.equal(h2, x2)
+        out[dt] = (torch.stack(x1), x2, joint)
+    for a64, a32 in zip(out[torch.float64], out[torch.float32]):                          # float32 restates the same network
+        assert float((a64 - a32.double()).abs().max()) < 5e-6 * max(1.0, float(a64.abs().max()))
+    # a stripe count beyond the map height is not a feature: the reference's empty slice cannot be pooled
+    with pytest.raises(RuntimeError):
+        eo.pooled(torch.ones(1, 8, 2, 1), 3)
