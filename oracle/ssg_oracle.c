@@ -534,7 +534,11 @@ static int cmp_pair_f(const void* a, const void* b) {
   const float i = ((const float*)a)[1], j = ((const float*)b)[1];
   return (i > j) - (i < j);
 }
-void ora_re_ranking_init(const float* dots, int N, int nq, int k1, int k2, float lambda_value, float* out) {
+/* the same with the stage boundaries the float32 HIP chain exposes (any of them may be NULL): rowmax_out [N] = max of every
+ * column of original_dist (== row, D is symmetric), rank_out [N, min(k1+1, N)] = initial_rank[:, :k1+1], vnnz_out [N] = entries of
+ * every row of V before the query expansion */
+void ora_re_ranking_init_stages(const float* dots, int N, int nq, int k1, int k2, float lambda_value, float* out, float* rowmax_out,
+                                int32_t* rank_out, int32_t* vnnz_out) {
   const size_t nn = (size_t)N * N;
   float* od = (float*)malloc(nn * 4);            /* original_dist = 2 - 2*dots, then transpose(od / max(od, axis=0)) */
   float* Dn = (float*)malloc(nn * 4);
@@ -556,6 +560,8 @@ void ora_re_ranking_init(const float* dots, int N, int nq, int k1, int k2, float
     }
     free(pr);
   }
+  if (rowmax_out) memcpy(rowmax_out, colmax, (size_t)N * 4);
+  if (rank_out) memcpy(rank_out, rank, (size_t)N * K * 4);
   float* V = (float*)calloc(nn, 4);
 #pragma omp parallel
   {
@@ -578,6 +584,7 @@ void ora_re_ranking_init(const float* dots, int N, int nq, int k1, int k2, float
       for (int a = 0; a < nu; a++) w[a] = expf(-Dn[(size_t)i * N + expn[a]]);
       const float sum = pairwise_sum_f32(w, nu);
       for (int a = 0; a < nu; a++) V[(size_t)i * N + expn[a]] = 1.f * w[a] / sum;
+      if (vnnz_out) vnnz_out[i] = nu;
     }
     free(rec); free(crec); free(expn); free(w);
   }
@@ -617,6 +624,9 @@ void ora_re_ranking_init(const float* dots, int N, int nq, int k1, int k2, float
   }
   if (Vq != V) free(Vq);
   free(V); free(rank); free(colmax); free(Dn); free(od); free(colptr); free(rows); free(fill);
+}
+void ora_re_ranking_init(const float* dots, int N, int nq, int k1, int k2, float lambda_value, float* out) {
+  ora_re_ranking_init_stages(dots, N, nq, k1, k2, lambda_value, out, NULL, NULL, NULL);
 }
 
 int ora_num_threads(void) {

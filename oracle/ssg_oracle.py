@@ -219,11 +219,58 @@ def re_ranking_init(query_feature, gallery_feature, k1=20, k2=6, lambda_value=0.
 
 def re_ranking_init_dist(q_g_dist, q_q_dist, g_g_dist, k1=20, k2=6, lambda_value=0.3):
     """reid/rerank_initial.py:40-99 (takes the three dot-product matrices)."""
-    dots = _c(np.concatenate([np.concatenate([q_q_dist, q_g_dist], axis=1), np.concatenate([q_g_dist.T, g_g_dist], axis=1)], axis=0), np.float32)
+    dots = stacked_dots(q_g_dist, q_q_dist, g_g_dist)
     N, nq = dots.shape[0], q_g_dist.shape[0]
     out = np.empty((nq, N - nq), np.float32)
     lib().ora_re_ranking_init(_p(dots, _f32p), N, nq, int(k1), int(k2), ctypes.c_float(lambda_value), _p(out, _f32p))
     return out
+
+
+def stacked_dots(q_g_dist, q_q_dist, g_g_dist):
+    """the [[q_q, q_g], [q_g^T, g_g]] float32 matrix re_ranking_init stacks (rerank.py:178-181)"""
+    return _c(np.concatenate([np.concatenate([q_q_dist, q_g_dist], axis=1), np.concatenate([q_g_dist.T, g_g_dist], axis=1)], axis=0), np.float32)
+
+
+def re_ranking_init_stages(dots, nq, k1=20, k2=6, lambda_value=0.3):
+    """re_ranking_init_dist on the stacked dot products, with the stage boundaries of the float32 chain:
+    -> (final [nq, N-nq], dict(rowmax [N] = np.max(original_dist, axis=0), rank [N, min(k1+1, N)] = the k1+1 smallest of every
+    normalised row in (value, column) order, v_nnz [N] = entries per row of V before the query expansion))."""
+    dots = _c(dots, np.float32)
+    N = dots.shape[0]
+    K = min(k1 + 1, N)
+    out = np.empty((nq, N - nq), np.float32)
+    rowmax = np.empty(N, np.float32); rank = np.empty((N, K), np.int32); v_nnz = np.empty(N, np.int32)
+    lib().ora_re_ranking_init_stages(_p(dots, _f32p), N, int(nq), int(k1), int(k2), ctypes.c_float(lambda_value), _p(out, _f32p),
+                                     _p(rowmax, _f32p), _p(rank, _i32p), _p(v_nnz, _i32p))
+    return out, dict(rowmax=rowmax, rank=rank, v_nnz=v_nnz)
+
+
+def sqdist_f64(x, y, form, rows=None, cols=None):
+    """float64 value of the three float32 distance forms on float32 inputs, for the sampled rows of x and columns (rows of y):
+    form 0: |x|^2 + |y|^2 - 2 x.y (evaluators.py:82-84), 1: 2 |x|^2 - 2 x.y (:70-71), 2: 2 - 2 x.y (rerank.py:182)."""
+    x = np.asarray(x, np.float64) if rows is None else np.asarray(x[rows], np.float64)
+    y = np.asarray(y, np.float64) if cols is None else np.asarray(y[cols], np.float64)
+    g = x @ y.T
+    if form == 0:
+        return (x * x).sum(1)[:, None] + (y * y).sum(1)[None, :] - 2.0 * g
+    if form == 1:
+        return 2.0 * (x * x).sum(1)[:, None] - 2.0 * g
+    return 2.0 - 2.0 * g
+
+
+def sqdist_f32_reference(x, y, form):
+    """the reference's own float32 arithmetic for the same three forms: torch on the CPU, the expressions of evaluators.py:70-71,
+    :82-84 and (numpy) rerank.py:174-182"""
+    import torch
+    x = torch.as_tensor(np.ascontiguousarray(x, np.float32)); y = torch.as_tensor(np.ascontiguousarray(y, np.float32))
+    m, n = x.size(0), y.size(0)
+    if form == 0:
+        dist = torch.pow(x, 2).sum(dim=1, keepdim=True).expand(m, n) + torch.pow(y, 2).sum(dim=1, keepdim=True).expand(n, m).t()
+        return torch.addmm(dist, x, y.t(), beta=1, alpha=-2).numpy()
+    if form == 1:
+        dist = torch.pow(x, 2).sum(dim=1, keepdim=True) * 2
+        return (dist.expand(m, n) - 2 * torch.mm(x, y.t())).numpy()
+    return 2. - 2 * np.dot(x.numpy(), np.transpose(y.numpy()))
 
 
 def re_ranking_plain(input_feature_source, input_feature, k=20, lambda_value=0.1, MemorySave=False, Minibatch=2000, stages=False):

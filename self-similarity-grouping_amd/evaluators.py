@@ -261,9 +261,12 @@ def _sqdist(x, y, self_form=False):
     from ._lib import check, ptr, stream
     L = _lib.lib()
     dev = torch.device("cuda", torch.cuda.current_device())
-    x = x.to(dev, torch.float32).contiguous(); y = y.to(dev, torch.float32).contiguous()
     m, d = x.shape; n = y.shape[0]
     dp, npad = (-d) % 32, (-n) % 64
+    if m * (d + dp) * 4 > 0x7fffffff:      # ask the entry point before anything is copied or allocated: it refuses from m, n and d alone
+        rc = L.ssg_pairwise_sqdist_f32(None, None, m, n + npad, d + dp, 1 if self_form else 0, None, None, None)
+        raise _lib.SSGError("ssg_pairwise_sqdist_f32 refused (%d): %s" % (rc, L.ssg_last_error().decode("utf-8", "replace")))
+    x = x.to(dev, torch.float32).contiguous(); y = y.to(dev, torch.float32).contiguous()
     if dp:
         x = torch.nn.functional.pad(x, (0, dp)); y = torch.nn.functional.pad(y, (0, dp))
     if npad:

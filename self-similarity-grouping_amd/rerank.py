@@ -610,14 +610,21 @@ def re_ranking_init_device(query_feature, gallery_feature, k1=20, k2=6, lambda_v
     [num_query, num_gallery] float32 CUDA tensor (the SSG++ label step, ssg_amd.eug, consumes it there)."""
     L = _lib.lib()
     device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    q = torch.as_tensor(query_feature).to(device, torch.float32); g = torch.as_tensor(gallery_feature).to(device, torch.float32)
+    q = torch.as_tensor(query_feature); g = torch.as_tensor(gallery_feature)
     nq, N = q.shape[0], q.shape[0] + g.shape[0]
+    if N * q.shape[1] * 4 > 0x7fffffff:    # ask the entry point before anything is copied or allocated: it refuses from m, n and d alone
+        rc = L.ssg_cosine_dist_f32(None, None, N, N + (-N) % 64, q.shape[1], None, None, None)
+        raise _lib.SSGError("ssg_cosine_dist_f32 refused (%d): %s" % (rc, L.ssg_last_error().decode("utf-8", "replace")))
+    q = q.to(device, torch.float32); g = g.to(device, torch.float32)
     x = _as_dev_f32(torch.cat([q, g], 0), device)
     npad = (-N) % 64
     y = torch.nn.functional.pad(x, (0, 0, 0, npad)) if npad else x
     zeros = torch.zeros(N + npad, dtype=torch.float32, device=device)
     Dp = torch.empty((N, N + npad), dtype=torch.float32, device=device)
-    check(L.ssg_cosine_dist_f32(ptr(x), ptr(y), N, N + npad, x.shape[1], ptr(zeros), ptr(Dp), stream()), "ssg_cosine_dist_f32")
+    try:
+        check(L.ssg_cosine_dist_f32(ptr(x), ptr(y), N, N + npad, x.shape[1], ptr(zeros), ptr(Dp), stream()), "ssg_cosine_dist_f32")
+    except ValueError as e:      # d % 32 != 0: a limit of the library's GEMM, reported like its other failures
+        raise _lib.SSGError(str(e)) from None
     D = Dp[:, :N].contiguous() if npad else Dp
     return _init_pipeline(D, nq, k1, k2, lambda_value)
 
