@@ -526,6 +526,27 @@ int ssg_allgather(void* comm, const void* send, void* recv, size_t bytes_per_ran
 int ssg_allreduce_sum_i64(void* comm, int64_t* buf, size_t count, ssg_stream_t stream);
 int ssg_comm_destroy(void* comm);
 
+/* DEC cluster head of the fine-tune phase (--dce-loss; reid/models/dce.py:39-51, reid/trainers.py:268-292; csrc/dec.hip).  float32 in
+ * and out, every D-long sum, column sum, row sum and the loss accumulated in float64 in a fixed order (no float atomics: the same
+ * call gives the same bits), no host read.  1 <= B <= 4096 rows, 1 <= K <= 64 centres, any D >= 1.
+ * Soft assignment: x [B, D] at row pitch ldx >= D (elements), c [K, D] -> q [B, K]:
+ *   ns[i,j] = sum_d (x[i,d] - c[j,d])^2,  n = (1 / (1 + ns/alpha)) ^ -(alpha+1)/2,  q[i,j] = n[i,j] / sum_j n[i,j]
+ * (alpha = 1: q ~ 1 + ns, the FARTHEST centre gets the largest weight -- what the reference trains with).  ns [B, K]: optional output
+ * (NULL: not written), the input of ssg_dec_assign_grad_f32. */
+int ssg_dec_assign_f32(const float* x, int64_t ldx, const float* c, int B, int K, int D, double alpha, float* q, float* ns,
+                       ssg_stream_t stream);
+/* Target distribution and loss: f[j] = sum_i q[i,j], w = q^2 / f, p[i,j] = w[i,j] / sum_j w[i,j] (p [B, K] optional output),
+ * loss[0] = sum_ij p (log p - log q) / B  (nn.KLDivLoss(size_average=False)(q.log(), p) / B; p == 0 contributes 0).  One launch. */
+int ssg_dec_kl_loss_f32(const float* q, int B, int K, float* p, float* loss, ssg_stream_t stream);
+/* gq [B, K] = gloss[0] * d loss / d q with p NOT detached (the reference's graph): through log q and through p.  gloss: device
+ * pointer to the upstream gradient of the loss.  One launch. */
+int ssg_dec_kl_loss_grad_f32(const float* q, int B, int K, const float* gloss, float* gq, ssg_stream_t stream);
+/* Backward of the assignment: gq [B, K] = d objective / d q, ns the forward's output -> gx [B, D] (dense), gc [K, D]:
+ *   g = d objective / d ns (float64, written to the workspace gns [B, K] doubles),
+ *   gx = 2 (rowsum(g) x - g c),  gc = 2 (colsum(g) c - g^T x)  -- no [B, K, D] temporary.  3 launches. */
+int ssg_dec_assign_grad_f32(const float* x, int64_t ldx, const float* c, const float* ns, const float* gq, int B, int K, int D, double alpha,
+                            double* gns, float* gx, float* gc, ssg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -52,6 +52,12 @@ def __getattr__(name):   # lazy: torch import only when the compute surface is t
     if name in ("GpuTrainLoader", "TrainTransform", "generate_dataloader"):
         from . import trainloader
         return getattr(trainloader, name)
+    if name in ("ClusterAssignment", "target_distribution", "kl_loss", "use_device_assignment", "soft_assignment"):
+        from . import dce
+        return getattr(dce, name)
+    if name in ("DECFinedTrainer2Mixin", "DECJointTrainer2Mixin"):
+        from . import trainers
+        return getattr(trainers, name)
     if name in ("create", "ResNet", "synthetic_state_dict"):
         from . import resnet
         return getattr(resnet, name)

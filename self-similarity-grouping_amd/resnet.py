@@ -6,14 +6,17 @@ reference's call surface: `state_dict()` / `load_state_dict()` with the referenc
 (`base.conv1.weight`, `base.layer1.0.bn2.running_var`, `feat.weight`, `feat_bn.*` ...),
 `eval()`, `cuda()`, and `model(x, for_eval)` -> `(x1, x2)` where x1 is the list of S+1
 pooled feature sets (or their concatenation when for_eval=True), resnet.py:86-134.
+`cluster=True` adds the DEC head (resnet.py:76-77,126-132): the key `assignment.cluster_centers`
+[32, 2048] and a third output x3 = soft assignment of x1 (csrc/dec.hip) wherever the reference
+returns one.
 
 The forward runs on hand-written HIP kernels (csrc/conv.hip) through the C ABI: NHWC fp32,
 eval-mode BatchNorm folded into the convolution weights at load time, bias/residual/ReLU
 fused into the GEMM epilogue.  precision='split' (default) carries every fp32 activation /
 weight as two halves (hi + lo, 22 significand bits) and evaluates the products on the fp16
 matrix cores with fp32 accumulation (include/ssg_hip.h, ssg_conv2d_nhwc_x); precision='f32'
-keeps everything on the fp32 matrix cores.  There is no training path here (fine-tuning is out of scope,
-SURVEY.md section 2 rows 10-11).
+keeps everything on the fp32 matrix cores.  There is no training path through the backbone here (SURVEY.md
+section 2 rows 10-11); the DEC head that trains is `ssg_amd.dce.ClusterAssignment`.
 """
 from collections import OrderedDict
 
@@ -27,6 +30,7 @@ from ._lib import check, ptr, stream
 
 _LAYERS = {50: (3, 4, 6, 3), 101: (3, 4, 23, 3), 152: (3, 8, 36, 3)}
 _BN_EPS = 1e-5
+_DEC_CLUSTERS, _DEC_DIM, _DEC_KEY = 32, 2048, "assignment.cluster_centers"      # resnet.py:77
 
 
 def _arch(depth):
@@ -42,7 +46,7 @@ def _arch(depth):
     return blocks
 
 
-def synthetic_state_dict(seed=1, depth=50, num_features=2048, randomize_bn=True):
+def synthetic_state_dict(seed=1, depth=50, num_features=2048, randomize_bn=True, cluster=False):
     """Deterministic random weights with the reference's shapes and key names: Kaiming-normal
     fan_out convolutions (reid/models/base.py:113-118), BatchNorm statistics drawn at random so
     that the BN folding is exercised (gamma ~ U(.5,1.5), beta, mean ~ N(0,.1), var ~ U(.5,1.5)).
@@ -80,6 +84,9 @@ def synthetic_state_dict(seed=1, depth=50, num_features=2048, randomize_bn=True)
         sd["feat_bn.weight"] = torch.ones(num_features); sd["feat_bn.bias"] = torch.zeros(num_features)
         sd["feat_bn.running_mean"] = torch.zeros(num_features); sd["feat_bn.running_var"] = torch.ones(num_features)
         sd["feat_bn.num_batches_tracked"] = torch.zeros((), dtype=torch.long)
+    if cluster:     # drawn last, so every other tensor is the one cluster=False gets; Xavier uniform like dce.py:29-34
+        bound = math.sqrt(6.0 / (_DEC_CLUSTERS + _DEC_DIM))
+        sd[_DEC_KEY] = (torch.rand(_DEC_CLUSTERS, _DEC_DIM, generator=g) * 2.0 - 1.0) * bound
     return sd
 
 
@@ -170,8 +177,6 @@ class ResNet:
                  mode='Dissimilarity', cluster=False, seed=1, precision=None):
         if depth not in _LAYERS:
             raise KeyError("Unsupported depth:", depth)
-        if cluster:
-            raise NotImplementedError("cluster=True (DEC head, reid/models/dce.py) is outside the grouping hot path")
         if num_classes > 0:
             raise NotImplementedError("num_classes > 0 (dropout + classifier head, resnet.py:118-120) is a training-only path; "
                                       "the grouping path uses num_classes=0 (selftraining.py:121-123)")
@@ -183,7 +188,7 @@ class ResNet:
         if self.precision not in ("split", "f32"):
             raise ValueError("precision must be 'split' or 'f32'")
         self.device = torch.device("cpu")
-        self._sd = synthetic_state_dict(seed, depth, num_features)
+        self._sd = synthetic_state_dict(seed, depth, num_features, cluster=bool(cluster))
         self._folded = None
         self._twin = None
         self.flip_streams = True         # embed_with_flip: the original and the flipped forward on two HIP streams (SSG_FLIP_STREAMS=0: one)
@@ -486,7 +491,20 @@ class ResNet:
         out = self._conv(_lib.lib(), gap.reshape(B, 1, 1, 2048).contiguous(), net["feat"], relu=True)
         return out.reshape(B, self.num_features)
 
+    def _x3(self, x1):
+        """x3 = assignment(x1) (resnet.py:131, dce.py:47-51: always alpha = 1) on the HIP kernel, centres cached on the device"""
+        from . import dce
+        net = self._prepare()
+        if "centers" not in net:
+            net["centers"] = self._sd[_DEC_KEY].to(self.device, torch.float32).contiguous()
+        return dce.soft_assignment(x1, net["centers"], 1.0)
+
     def __call__(self, x, for_eval=False):
+        if self.cluster and self.num_split > 1 and not for_eval:
+            # resnet.py:129: the reference concatenates the (S+1) pooled sets and dies in broadcasting against the 2048-wide centres
+            raise ValueError("cluster=True with num_split=%d and for_eval=False: the reference assigns the concatenated [B, %d] features to "
+                             "%d-wide cluster centres, a shape mismatch (reid/models/resnet.py:129)"
+                             % (self.num_split, (self.num_split + 1) * _DEC_DIM, _DEC_DIM))
         sets = self.pooled(*self._fmap(x))
         if self._overflowed():
             return self._f32_twin()(x, for_eval)
@@ -496,6 +514,8 @@ class ResNet:
             if for_eval:
                 return torch.cat(x1, dim=1), x2
             return x1, x2
+        if self.cluster:
+            return sets[0], x2, self._x3(sets[0])
         return sets[0], x2
 
     forward = __call__

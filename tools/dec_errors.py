@@ -1,0 +1,38 @@
+#!/usr/bin/env python3
+"""Write profiles/dec_errors.txt (run on the MI355X): for every case of tests/test_gpu_dec.py and every output of the four DEC entry
+points, and of the autograd chain ClusterAssignment -> kl_loss -> backward ("chain" rows), err_dev = max |device - ref64| / max |ref64| and err_f32, the same measure for tests/dec_ref.py run in float32 on the CPU, and
+their ratio.  The test's factor F is the next power of two above the worst ratio (at most 4).  Where err_dev <= 2^-24 -- the
+rounding of the float32 output, which the criterion allows by itself -- the ratio is shown but does not count."""
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "tests")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+
+def main():
+    import torch
+    import test_gpu_dec as t
+    out = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "dec_errors.txt")
+    lines = ["DEC entry points (csrc/dec.hip) on %s: error against tests/dec_ref.py in float64, next to the float32 torch chain's" % torch.cuda.get_device_name(0),
+             "err = max|v - ref64| / max|ref64|; ratio = err_dev / err_f32; '*': err_dev > 2^-24 = %.3e, the ratio counts" % t.FLOOR,
+             "%-14s %-20s %-10s %11s %11s %9s" % ("case", "(B, K, D) scale", "output", "err_dev", "err_f32", "ratio")]
+    worst = 0.0
+    for name in t.CASES:
+        B, K, D, scale = t.CASES[name][:4]
+        for n, e_dev, e_f32 in t.measure(name) + (t.measure_chain(name) if name in t.CHAIN_CASES else []):
+            ratio = e_dev / e_f32 if e_f32 > 0 else float("inf") if e_dev > 0 else 0.0
+            counts = e_dev > t.FLOOR
+            if counts:
+                worst = max(worst, ratio)
+            lines.append("%-14s %-20s %-10s %11.3e %11.3e %9.3g%s" % (name, "(%d, %d, %d) %g" % (B, K, D, scale), n, e_dev, e_f32, ratio, " *" if counts else ""))
+    lines.append("worst counting ratio: %.3g" % worst)
+    with open(out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    print("\n".join(lines))
+
+
+if __name__ == "__main__":
+    main()
