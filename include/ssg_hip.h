@@ -368,6 +368,39 @@ int ssg_knn_sets(const uint16_t* D, const int32_t* rank, int N, int row0, int nr
 int ssg_set_jaccard_rows(const int32_t* a_idx, const int32_t* a_nnz, int capA, const int64_t* colptr, const int32_t* inv_row, int N, int row0,
                          int nrows, uint16_t one_minus_lambda_half, uint16_t* Jp, ssg_stream_t stream);
 
+/* ---- Hausdorff re-ranking variant (reid/rerank_hausdorff.py:7-65 re_ranking; csrc/hausdorff.hip; shares the half original distance
+ * and the kNN sets -- ssg_knn_sets -- with the kNN-set variant).  Everything below is float64 on the vector ALU with no fused
+ * multiply-add, in the one order scipy's cdist and directed_hausdorff use, so the results are the reference's bit for bit. */
+/* out[i, j] = s or sqrt(s) (take_sqrt != 0, correctly rounded) for x [m, d], y [n, d] float32, out float64 at row pitch ld >= n
+ * (elements):  s = 0; for c = 0 .. d-1: t = f64(x[i,c]) - f64(y[j,c]); s = s + t * t.  Any m, n, d >= 1. */
+int ssg_seqdist_f64(const float* x, int m, const float* y, int n, int d, int take_sqrt, double* out, int64_t ld, ssg_stream_t stream);
+/* the same for y = x: only the 64 x 64 tiles on or above the diagonal are computed, the others are their mirror images
+ * ((a-b)^2 == (b-a)^2 bit for bit): out is exactly symmetric with a zero diagonal */
+int ssg_seqdist_self_f64(const float* x, int n, int d, int take_sqrt, double* out, int64_t ld, ssg_stream_t stream);
+/* rowmin[i] = min_j s[i, j] (the squared sum; the m x n block is never written) */
+int ssg_seqdist_rowmin_f64(const float* x, int m, const float* y, int n, int d, double* rowmin, ssg_stream_t stream);
+/* vec = sqrt(rowmin); *vmax = max(vec); vec = vec / max(vec)  (:14-15).  *vmax == 0: the reference divides 0/0, the caller must raise. */
+int ssg_hausdorff_source_finish(const double* rowmin, int N, double* vec, double* vmax, ssg_stream_t stream);
+/* Directed distances G[i, j] = max_{b in S_j} min_{a in S_i} E[a, b] for rows i in [row0, row0+nrows) of the full N x N matrix G
+ * (G[i, i] = 0).  E [N, N] float64 MUST be exactly symmetric (ssg_seqdist_self_f64); a_idx [N, cap] / a_nnz [N] = the sets of all N
+ * rows as ssg_knn_sets writes them (non-empty; an empty S_j gives 0).  The table is trusted, not
+ * validated: a_nnz is clamped to cap and an index outside [0, N) is skipped so that a damaged table cannot read out of bounds, but
+ * the result is then meaningless and no error is reported.  ws: ssg_hausdorff_workspace_bytes(N, nrows) bytes.
+ * N * N < 2^31. */
+size_t ssg_hausdorff_workspace_bytes(int N, int nrows);
+int ssg_hausdorff_directed_rows(const double* E, const int32_t* a_idx, const int32_t* a_nnz, int cap, int N, int row0, int nrows, double* G,
+                                void* ws, size_t ws_bytes, ssg_stream_t stream);
+/* H = max(G, G^T) in place once every row of G is there (:57-58: the other direction of the pair (i, j) is G[j, i] because E is
+ * symmetric); *hmax = max(H).  *hmax == 0: the reference divides 0/0 at :60, the caller must raise. */
+int ssg_hausdorff_symmetrize(double* G, int N, double* hmax, ssg_stream_t stream);
+/* out[il, j] = (H[il, j] / *hmax) * one_minus_lambda + (vec[j] + vec[row0+il]) * lambda_value, each operation rounded on its own
+ * (:60-62; one_minus_lambda = 1 - lambda computed by the host in float64).  H, out: rows [row0, row0+nrows); out may be H. */
+int ssg_hausdorff_blend(const double* H, const double* hmax, const double* vec, int N, int row0, int nrows, double one_minus_lambda,
+                        double lambda_value, double* out, ssg_stream_t stream);
+/* out = D / max(D) in numpy's half arithmetic (:41) for the whole half matrix D [N, N]; rowmax [N] = its row maxima as half bits;
+ * *gmax (one word of workspace) receives max(D) as half bits */
+int ssg_half_div_max(const uint16_t* D, const uint32_t* rowmax, int N, uint16_t* out, uint32_t* gmax, ssg_stream_t stream);
+
 /* ---- retrieval metrics of the evaluation step (reid/evaluators.py:88-129 evaluate_all ->
  * reid/evaluation_metrics/ranking.py:18-79 cmc, :82-115 mean_ap + sklearn average_precision_score) */
 /* dist [m, ld] float32 query x gallery block; ids / cams int32.  first_rank[q] = number of valid gallery entries

@@ -34,6 +34,9 @@ def __getattr__(name):   # lazy: torch import only when the compute surface is t
     if name in ("re_ranking_plain", "re_ranking_plain_device"):
         from . import rerank_plain
         return rerank_plain.re_ranking if name == "re_ranking_plain" else rerank_plain.re_ranking_plain_device
+    if name in ("re_ranking_hausdorff", "re_ranking_hausdorff_device"):
+        from . import rerank_hausdorff
+        return rerank_hausdorff.re_ranking if name == "re_ranking_hausdorff" else rerank_hausdorff.re_ranking_hausdorff_device
     if name in ("cmc", "mean_ap", "evaluate_all", "Evaluator"):
         from . import ranking
         return getattr(ranking, name)

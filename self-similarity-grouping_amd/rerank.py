@@ -30,7 +30,8 @@ class DistHandle:
 
     mode 0: final_dist[i,k] = f64(Jp[i,k]) + f64(half(v[i]+v[k])) * lambda   (rerank.py:122)
     mode 1: no-rerank: the half euclidean matrix itself (rerank.py:65-66)
-    mode 2: an arbitrary float64 matrix uploaded by the caller (sklearn drop-in case)
+    mode 2: a float64 matrix held as it is: uploaded by the caller (sklearn drop-in case) or the final_dist of the Hausdorff variant
+            (rerank_hausdorff.re_ranking_hausdorff_device, which also sets `euclid`)
     Rows [row0, row0+nrows) of the N x N problem are held locally (row-block sharding).
 
     Sharded handles (group is not None): `validate`, `final_dist`, `cluster.eps_rule`, `cluster.eps_rule_dbscan` and `DBSCAN.fit` are

@@ -20,7 +20,11 @@ def _dev():
     return torch.device("cuda", torch.cuda.current_device())
 
 
-def compute_dist(source_features, target_features, lambda_value, no_rerank, num_split=2, materialize=False, group=None, grouping="auto"):
+VARIANTS = ("kreciprocal", "plain", "hausdorff")
+
+
+def compute_dist(source_features, target_features, lambda_value, no_rerank, num_split=2, materialize=False, group=None, grouping="auto",
+                 variant="kreciprocal", k=20, memory_save=False):
     """selftraining.py:255-277.  Features: torch tensors (CPU or CUDA) or numpy arrays,
     a list of S+1 per-split tensors or a single tensor.  Returns (euclidean_dist_list,
     rerank_dist_list) with one entry per split.
@@ -28,7 +32,17 @@ def compute_dist(source_features, target_features, lambda_value, no_rerank, num_
     group (torch.distributed) + grouping: 'shard' = every rank computes its `shard_bounds` row block and the small tables are
     all-gathered; 'replicate' = every rank runs the whole problem on its own GPU with no collective at all (the features are
     replicated on every rank anyway) -- identical handles, identical labels on every rank; 'auto' (default) = `dist.choose_grouping`:
-    the form its time model predicts to be faster for this N and world size (small problems replicate)."""
+    the form its time model predicts to be faster for this N and world size (small problems replicate).
+
+    variant: which of the reference's three re-rank distances -- 'kreciprocal' (reid/rerank.py, the default: today's path),
+    'plain' (reid/rerank_plain.py) or 'hausdorff' (reid/rerank_hausdorff.py).  The last two run on one GPU only (group must be
+    None); `k` and `memory_save` (the reference's k and MemorySave) reach these two only -- the default variant keeps its own k1 / k2;
+    their handles go on to `generate_selflabel` like the default's.  With no_rerank=True no re-rank distance is computed, so the
+    variant makes no difference: every variant returns the same euclidean handles."""
+    if variant not in VARIANTS:
+        raise ValueError("compute_dist: variant must be one of %r, got %r" % (VARIANTS, variant))
+    if variant != "kreciprocal" and group is not None:
+        raise ValueError("compute_dist: variant=%r runs on a single GPU (group must be None)" % (variant,))
     euclidean_dist_list, rerank_dist_list = [], []
     if not isinstance(source_features, list):
         source_features, target_features = [source_features], [target_features]
@@ -42,8 +56,15 @@ def compute_dist(source_features, target_features, lambda_value, no_rerank, num_
             if choose_grouping(t.shape[0], dist.get_world_size(group), grouping) == "shard":
                 row0, row1 = shard_bounds(t.shape[0], dist.get_rank(group), dist.get_world_size(group))   # ragged N allowed
                 nrows, grp = row1 - row0, group
-        h = re_ranking_device(s, t, lambda_value=lambda_value, no_rerank=no_rerank, keep_euclid=no_rerank, row0=row0, nrows=nrows, group=grp,
-                              validate=materialize)     # fused path: the status words are read by generate_selflabel's first round trip
+        if variant != "kreciprocal" and not no_rerank:
+            if variant == "plain":
+                from .rerank_plain import re_ranking_plain_device as other
+            else:
+                from .rerank_hausdorff import re_ranking_hausdorff_device as other
+            h = other(s, t, k=k, lambda_value=lambda_value, memory_save=memory_save)
+        else:
+            h = re_ranking_device(s, t, lambda_value=lambda_value, no_rerank=no_rerank, keep_euclid=no_rerank, row0=row0, nrows=nrows, group=grp,
+                                  validate=materialize)     # fused path: the status words are read by generate_selflabel's first round trip
         if materialize:
             from . import hostio
             if no_rerank:
