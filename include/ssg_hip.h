@@ -580,6 +580,32 @@ int ssg_dec_kl_loss_grad_f32(const float* q, int B, int K, const float* gloss, f
 int ssg_dec_assign_grad_f32(const float* x, int64_t ldx, const float* c, const float* ns, const float* gq, int B, int K, int D, double alpha,
                             double* gns, float* gx, float* gc, ssg_stream_t stream);
 
+/* ---- verification metrics (reid/evaluation_metrics/eval_far_gar.py:61-202; csrc/verify.hip) ------------------------------
+ * D [m, n] float32 SQUARED distances at row pitch ld >= n (elements; m * ld * 4 may exceed 2^32), qlab int32 [m], rlab int32 [n], all on
+ * the device and only read.  Element (i, j) is intra when rlab[j] == qlab[i], else inter (no camera filter); every element is taken as
+ * s = sqrtf(d <= 0 ? 0 : d), correctly rounded.  ws: ssg_verify_workspace_bytes(m, n) bytes (8-byte aligned), shared by the three
+ * passes, which must not run concurrently on it.  Each pass streams the block once per launch noted below and writes nothing into it.
+ * No float atomics: the same call gives the same bits.  Bad arguments are refused (-1) before any launch. */
+size_t ssg_verify_workspace_bytes(int m, int n);
+/* Pass A.  counts[2] = {intra, inter} int64; sums[4] = {sum s, sum s^2 of intra, sum s, sum s^2 of inter} float64 (s widened before
+ * squaring; per-workgroup partials added in index order); minmax[4] = {intra min, intra max, inter min, inter max} float32;
+ * status[0] = 1 when some query row has no intra or no inter element, status[1] = 1 when a NaN was seen.  2 launches. */
+int ssg_verify_stats_f32(const float* D, int m, int n, size_t ld, const int32_t* qlab, const int32_t* rlab, void* ws, size_t ws_bytes,
+                         int64_t* counts, double* sums, float* minmax, int32_t* status, ssg_stream_t stream);
+/* Pass B.  ranks_host: nr (1 .. 64) zero-based ranks, a HOST array, each >= 0.  values[r] = np.sort(inter s)[ranks[r]] exactly (a
+ * four-level radix select on the bit patterns, all ranks in the same 4 passes; a rank inside a run of equal values returns that value).
+ * status[0] = 1 when a rank is >= the number of inter elements (every value is then NaN).  8 launches. */
+int ssg_verify_select_f32(const float* D, int m, int n, size_t ld, const int32_t* qlab, const int32_t* rlab, const int64_t* ranks_host, int nr,
+                          void* ws, size_t ws_bytes, float* values, int32_t* status, ssg_stream_t stream);
+/* Pass C.  thr_host: nt (1 .. 64) float64 thresholds, a HOST array in any order, none NaN.  counts [3, nt] int64: row 0 = intra with
+ * s >= t, row 1 = inter with s < t, row 2 = intra with s < t, compared in double.  totals[2] = {intra, inter} element counts.
+ * is_sq = 1: s as above; is_sq = 0: the block is compared as stored, no clamp and no sqrt (CalClassificationError_MPI with dist=).
+ * NaN elements count in totals only.  2 launches. */
+int ssg_verify_count_f32(const float* D, int m, int n, size_t ld, const int32_t* qlab, const int32_t* rlab, int is_sq, const double* thr_host,
+                         int nt, void* ws, size_t ws_bytes, int64_t* counts, int64_t* totals, ssg_stream_t stream);
+/* s[i] = the value the three passes take for a stored d[i] (parity suite: equals numpy's float32 sqrt bit for bit). */
+int ssg_selftest_verify_sqrt(const float* d, int n, float* s, ssg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -140,8 +140,20 @@ def evaluate_all(distmat, query=None, gallery=None, query_ids=None, gallery_ids=
     return scores[0]
 
 
+def evaluate_same_cams_all(distmat, query=None, gallery=None, query_ids=None, gallery_ids=None, cmc_topk=(1, 5, 10)):
+    """reid/evaluators.py:137-180: evaluate_all with the camera filter switched off (every query on camera 0, every gallery entry on
+    camera 1).  The reference's branch that takes the id lists directly leaves the cameras undefined (:145-149, a NameError); the
+    same 0 / 1 cameras are used here."""
+    if query is not None and gallery is not None:
+        query_ids = [pid for _, pid, _ in query]; gallery_ids = [pid for _, pid, _ in gallery]
+    else:
+        assert (query_ids is not None and gallery_ids is not None)
+    return evaluate_all(distmat, query_ids=query_ids, gallery_ids=gallery_ids, query_cams=[0] * len(query_ids),
+                        gallery_cams=[1] * len(gallery_ids), cmc_topk=cmc_topk)
+
+
 class Evaluator(object):
-    """reid/evaluators.py:147-166: features -> query x gallery distance block -> metrics, all on the GPU."""
+    """reid/evaluators.py:183-207: features -> query x gallery distance block -> metrics, all on the GPU."""
 
     def __init__(self, model, print_freq=1):
         self.model = model
@@ -152,3 +164,16 @@ class Evaluator(object):
         features, _ = extract_features(self.model, data_loader, print_freq=self.print_freq)
         distmat = pairwise_distance_device(features, query, gallery, metric=metric)
         return evaluate_all(distmat, query=query, gallery=gallery)
+
+    def evaluate_same_cams(self, data_loader, query, gallery, metric=None):
+        """reid/evaluators.py:194-207: the verification protocol (ssg_amd.verification.find_metric_threshold), then mAP / CMC without
+        the camera filter.  The distance block is computed once and stays on the device for both; as in the reference the
+        verification step sees the features without `metric`, so a metric costs a second block."""
+        from .evaluators import extract_features, pairwise_distance_device
+        from .verification import find_metric_threshold
+        features, _ = extract_features(self.model, data_loader)
+        query_ids = [pid for _, pid, _ in query]; gallery_ids = [pid for _, pid, _ in gallery]
+        distmat = pairwise_distance_device(features, query, gallery, metric=metric)
+        plain = distmat if metric is None else pairwise_distance_device(features, query, gallery)
+        find_metric_threshold(None, query_ids, None, gallery_ids, dist=plain)
+        return evaluate_same_cams_all(distmat, query=query, gallery=gallery)
