@@ -328,6 +328,16 @@ int ssg_bottleneck_nhwc_x(const void* x, const void* w1, const float* b1, const 
 int ssg_bottleneck_ds_nhwc_x(const void* x, const void* w1, const float* b1, const float* cs1, const void* w2, const float* b2, const float* cs2,
                              const void* w3cat, const float* b3, const float* cs3, void* out, int B, int H, int W, int CIN, int C, int MID,
                              int32_t* overflow, ssg_stream_t stream);
+/* One identity BasicBlock of ResNet-18 / ResNet-34 (base.py:25-54 without a downsample branch, stride 1) in ONE launch, split-half
+ * tensors: out = relu(conv2_3x3(relu(conv1_3x3(x) + b1)) + b2 + x).  x / out [B,H,W,C] h8l8 (out must not alias x); w1 / w2 [C][9*C]
+ * (k = (32-channel chunk, tap, channel)) as ssg_conv2d_nhwc_x takes them, rows pre-multiplied by powers of two that cs1 / cs2 undo;
+ * b* fp32 folded BatchNorm biases.  Bit-identical to the two ssg_conv2d_nhwc_x launches (the range flag included: it goes up for
+ * the intermediate as well as for the output); the C-channel intermediate stays in LDS and x is read from HBM once.
+ * ssg_basicblock_supported(): W == 32, C == 64, H % 4 == 0 (layer1 of both networks at 128-wide input); any other shape is refused
+ * before a launch. */
+int ssg_basicblock_supported(int H, int W, int C);
+int ssg_basicblock_nhwc_x(const void* x, const void* w1, const float* b1, const float* cs1, const void* w2, const float* b2, const float* cs2,
+                          void* out, int B, int H, int W, int C, int32_t* overflow, ssg_stream_t stream);
 /* The stem in ONE launch (base.py:101-105 conv1 + bn1 + relu + maxpool, with the fliplr of evaluators.py:12-16 folded into the
  * image read): images [B,3,H,W] float32 NCHW -> out [B,H/4,W/4,64] h8l8.  w [64][224] / bias / ch_scale: the stem weights as
  * ssg_conv2d_nhwc_x takes them (Cin = 4 "h4l4" layout).  Bit-identical to ssg_nchw_to_nhwc4_h4l4 + ssg_conv2d_nhwc_x +

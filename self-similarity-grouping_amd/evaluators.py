@@ -171,9 +171,10 @@ def extract_embeddings(model, data_loader, for_eval=False, print_freq=0, group=N
             print('Extract Features: [{}/{}]\tTime {:.3f}'.format(i + 1, nb, time.time() - t0))
     nsets = (m.num_split + 1) if m.num_split > 1 else 1
     three = nsets > 1 and not for_eval
+    width = getattr(m, "out_planes", 2048)                      # backbone width: 512 (resnet18 / 34) or 2048
     if ov is not None:
         for _ in range(len(chunks), ov["nb"]):                 # ranks with fewer batches still take part in every collective
-            post(None, (nsets, 2048) if three else (nsets * 2048,))
+            post(None, (nsets, width) if three else (nsets * width,))
     redo = bool(again and m._overflowed()) if ov is None else False
     if ov is not None and again:
         # the range flag of EVERY rank (one small gather + the one read the deferred check costs anyway): the pieces already travelled,
@@ -195,7 +196,7 @@ def extract_embeddings(model, data_loader, for_eval=False, print_freq=0, group=N
     if chunks:
         feats = torch.cat(chunks, dim=1 if chunks[0].dim() == 3 else 0)
     else:       # more ranks than batches: an empty share of the right shape
-        feats = torch.empty((nsets, 0, 2048) if three else (0, nsets * 2048), dtype=torch.float32, device=m.device)
+        feats = torch.empty((nsets, 0, width) if three else (0, nsets * width), dtype=torch.float32, device=m.device)
     if group is None or not gather:
         return feats, fnames, pids
     import torch.distributed as dist

@@ -1,5 +1,6 @@
-"""ResNet-50 embedder -- host-side mirror of reid/models/resnet.py (wrapper, :17-148) over the
-torchvision ResNet-50 architecture spelled out in reid/models/base.py:57-152.
+"""ResNet embedder -- host-side mirror of reid/models/resnet.py (wrapper, :17-148) over the
+torchvision ResNet architectures spelled out in reid/models/base.py:25-152: the Bottleneck depths 50 / 101 / 152 (2048-wide
+features) and the BasicBlock depths 18 / 34 (512-wide features).
 
 `create('resnet50', num_classes=0, num_split=S, cluster=False)` returns an object with the
 reference's call surface: `state_dict()` / `load_state_dict()` with the reference's key names
@@ -28,21 +29,31 @@ import torch
 from . import _lib
 from ._lib import check, ptr, stream
 
-_LAYERS = {50: (3, 4, 6, 3), 101: (3, 4, 23, 3), 152: (3, 8, 36, 3)}
+_LAYERS = {18: (2, 2, 2, 2), 34: (3, 4, 6, 3), 50: (3, 4, 6, 3), 101: (3, 4, 23, 3), 152: (3, 8, 36, 3)}
+_BASIC = (18, 34)                 # BasicBlock networks (base.py:25-54, expansion 1); the others are Bottleneck networks (expansion 4)
 _BN_EPS = 1e-5
 _DEC_CLUSTERS, _DEC_DIM, _DEC_KEY = 32, 2048, "assignment.cluster_centers"      # resnet.py:77
+_FUSED_BASICBLOCK_DEFAULT = "1"   # SSG_FUSED_BASICBLOCK: the layer1 blocks of ResNet-18 / -34 as one launch each (csrc/basicblock.hip)
+
+
+def _expansion(depth):
+    return 1 if depth in _BASIC else 4
 
 
 def _arch(depth):
-    """[(prefix, cin, cout, k, stride, pad)] conv list + block structure of a Bottleneck ResNet."""
+    """block structure of a ResNet (base.py:120-135 _make_layer): per block its key prefix, kind ('basic': conv1 3x3 stride s,
+    conv2 3x3; 'bottleneck': conv1 1x1, conv2 3x3 stride s, conv3 1x1), input / inner planes, stride and whether it has a
+    downsample branch (1x1 stride s; in a BasicBlock network only the first blocks of layer2-4)."""
     blocks = []
     inplanes = 64
+    exp = _expansion(depth)
+    kind = "basic" if exp == 1 else "bottleneck"
     for li, (planes, n) in enumerate(zip((64, 128, 256, 512), _LAYERS[depth])):
         for b in range(n):
             stride = 2 if (b == 0 and li > 0) else 1
-            down = b == 0 and (stride != 1 or inplanes != planes * 4)
-            blocks.append(dict(prefix="base.layer%d.%d" % (li + 1, b), inplanes=inplanes, planes=planes, stride=stride, down=down))
-            inplanes = planes * 4
+            down = b == 0 and (stride != 1 or inplanes != planes * exp)
+            blocks.append(dict(prefix="base.layer%d.%d" % (li + 1, b), kind=kind, inplanes=inplanes, planes=planes, stride=stride, down=down))
+            inplanes = planes * exp
     return blocks
 
 
@@ -70,17 +81,24 @@ def synthetic_state_dict(seed=1, depth=50, num_features=2048, randomize_bn=True,
         sd[name + ".num_batches_tracked"] = torch.zeros((), dtype=torch.long)
 
     conv("base.conv1", 64, 3, 7); bn("base.bn1", 64)
+    width = 512 * _expansion(depth)
     for blk in _arch(depth):
         p, ip, pl = blk["prefix"], blk["inplanes"], blk["planes"]
+        if blk["kind"] == "basic":
+            conv(p + ".conv1", pl, ip, 3); bn(p + ".bn1", pl)
+            conv(p + ".conv2", pl, pl, 3); bn(p + ".bn2", pl)
+            if blk["down"]:
+                conv(p + ".downsample.0", pl, ip, 1); bn(p + ".downsample.1", pl)
+            continue
         conv(p + ".conv1", pl, ip, 1); bn(p + ".bn1", pl)
         conv(p + ".conv2", pl, pl, 3); bn(p + ".bn2", pl)
         conv(p + ".conv3", pl * 4, pl, 1); bn(p + ".bn3", pl * 4)
         if blk["down"]:
             conv(p + ".downsample.0", pl * 4, ip, 1); bn(p + ".downsample.1", pl * 4)
-    sd["base.fc.weight"] = torch.randn(1000, 2048, generator=g) * 0.01
+    sd["base.fc.weight"] = torch.randn(1000, width, generator=g) * 0.01
     sd["base.fc.bias"] = torch.zeros(1000)
     if num_features > 0:
-        sd["feat.weight"] = torch.randn(num_features, 2048, generator=g) * 0.001      # init.normal_(std=0.001) resnet.py:67
+        sd["feat.weight"] = torch.randn(num_features, width, generator=g) * 0.001      # init.normal_(std=0.001) resnet.py:67
         sd["feat_bn.weight"] = torch.ones(num_features); sd["feat_bn.bias"] = torch.zeros(num_features)
         sd["feat_bn.running_mean"] = torch.zeros(num_features); sd["feat_bn.running_var"] = torch.ones(num_features)
         sd["feat_bn.num_batches_tracked"] = torch.zeros((), dtype=torch.long)
@@ -183,6 +201,7 @@ class ResNet:
         if num_features > 0 and num_features % 64:
             raise ValueError("num_features must be a multiple of 64")
         self.depth, self.num_features, self.dropout, self.num_classes = depth, num_features, dropout, num_classes
+        self.out_planes = 512 * _expansion(depth)       # backbone width (resnet.py:58 base.fc.in_features): 512 or 2048
         self.num_split, self.cluster, self.pretrained, self.training = num_split, cluster, pretrained, False
         self.precision = precision or os.environ.get("SSG_EMBED_PRECISION", "split")
         if self.precision not in ("split", "f32"):
@@ -276,6 +295,13 @@ class ResNet:
         net = dict(stem=_fold(sd, "base.conv1", "base.bn1", 2, 3, dev, split=sp), blocks=[], split=sp)
         for blk in _arch(self.depth):
             p = blk["prefix"]
+            if blk["kind"] == "basic":
+                net["blocks"].append(dict(
+                    kind="basic",
+                    c1=_fold(sd, p + ".conv1", p + ".bn1", blk["stride"], 1, dev, split=sp),
+                    c2=_fold(sd, p + ".conv2", p + ".bn2", 1, 1, dev, split=sp),
+                    ds=_fold(sd, p + ".downsample.0", p + ".downsample.1", blk["stride"], 0, dev, split=sp) if blk["down"] else None))
+                continue
             if blk["down"]:
                 # downsample branch fused into conv3: one GEMM over K = planes + inplanes (the residual tensor
                 # is never written to / re-read from HBM); both halves share one weight scale
@@ -341,8 +367,23 @@ class ResNet:
                   "ssg_bottleneck_ds_nhwc_x")
         return out
 
+    @staticmethod
+    def _basicblock(L, y, blk, ovf=None):
+        """whole identity BasicBlock in one launch (ssg_basicblock_nhwc_x); None when there is no fused kernel for this block
+        (stride-2 / downsample blocks, other shapes) or SSG_FUSED_BASICBLOCK=0"""
+        B, H, W, C = y.shape
+        c1, c2 = blk["c1"], blk["c2"]
+        if os.environ.get("SSG_FUSED_BASICBLOCK", _FUSED_BASICBLOCK_DEFAULT) == "0" or c1.stride != 1 or blk["ds"] is not None or c1.cout != C:
+            return None
+        if not L.ssg_basicblock_supported(H, W, C):
+            return None
+        out = torch.empty((B, H, W, C), dtype=torch.float32, device=y.device)
+        check(L.ssg_basicblock_nhwc_x(ptr(y), ptr(c1.w), ptr(c1.bias), ptr(c1.cscale), ptr(c2.w), ptr(c2.bias), ptr(c2.cscale), ptr(out),
+                                      B, H, W, C, ptr(ovf), stream()), "ssg_basicblock_nhwc_x")
+        return out
+
     def _fmap(self, x, flip=False, hooks=None):
-        """-> (layer4 map [B,h,w,2048], is_split): with precision='split' the float32 tensor is a container of
+        """-> (layer4 map [B,h,w,out_planes], is_split): with precision='split' the float32 tensor is a container of
         h8l8 split halves (decode with ssg_h8l8_decode).  hooks: {block index: callable} run on the host in front of that block's
         launches (the staggered two-stream schedule records / waits for its events there)."""
         L = _lib.lib()
@@ -380,6 +421,15 @@ class ResNet:
         for bi, blk in enumerate(blocks):
             if hooks and bi in hooks:
                 hooks[bi]()
+            if blk.get("kind") == "basic":      # base.py:38-54
+                fused = self._basicblock(L, y, blk, ovf) if sp else None
+                if fused is not None:
+                    y = fused
+                    continue
+                o = self._conv(L, y, blk["c1"], out_split=sp, ovf=ovf)
+                r = y if blk["ds"] is None else self._conv(L, y, blk["ds"], relu=False, out_split=sp, ovf=ovf)
+                y = self._conv(L, o, blk["c2"], res=r, relu=True, out_split=sp, ovf=ovf)
+                continue
             if sp:
                 fused = self._bottleneck(L, y, blk, ovf)
                 if fused is not None:
@@ -483,12 +533,12 @@ class ResNet:
         net = self._prepare()
         if "feat" not in net:
             sd = dict(self._sd)
-            sd["feat.weight4"] = sd["feat.weight"].view(self.num_features, 2048, 1, 1)
+            sd["feat.weight4"] = sd["feat.weight"].view(self.num_features, self.out_planes, 1, 1)
             f = _fold({"c.weight": sd["feat.weight4"], "b.weight": sd["feat_bn.weight"], "b.bias": sd["feat_bn.bias"],
                        "b.running_mean": sd["feat_bn.running_mean"], "b.running_var": sd["feat_bn.running_var"]}, "c", "b", 1, 0, self.device)
             net["feat"] = f
         B = gap.shape[0]
-        out = self._conv(_lib.lib(), gap.reshape(B, 1, 1, 2048).contiguous(), net["feat"], relu=True)
+        out = self._conv(_lib.lib(), gap.reshape(B, 1, 1, self.out_planes).contiguous(), net["feat"], relu=True)
         return out.reshape(B, self.num_features)
 
     def _x3(self, x1):
@@ -504,7 +554,11 @@ class ResNet:
             # resnet.py:129: the reference concatenates the (S+1) pooled sets and dies in broadcasting against the 2048-wide centres
             raise ValueError("cluster=True with num_split=%d and for_eval=False: the reference assigns the concatenated [B, %d] features to "
                              "%d-wide cluster centres, a shape mismatch (reid/models/resnet.py:129)"
-                             % (self.num_split, (self.num_split + 1) * _DEC_DIM, _DEC_DIM))
+                             % (self.num_split, (self.num_split + 1) * self.out_planes, _DEC_DIM))
+        if self.cluster and self.num_split <= 1 and self.out_planes != _DEC_DIM:
+            # resnet.py:129-131: the reference subtracts the 2048-wide centres from the 512-wide features and dies in broadcasting
+            raise ValueError("cluster=True on a %d-wide backbone (resnet%d): the reference assigns [B, %d] features to %d-wide cluster "
+                             "centres, a shape mismatch (reid/models/resnet.py:129-131)" % (self.out_planes, self.depth, self.out_planes, _DEC_DIM))
         sets = self.pooled(*self._fmap(x))
         if self._overflowed():
             return self._f32_twin()(x, for_eval)
@@ -558,6 +612,14 @@ class ResNet:
         return out
 
 
+def resnet18(**kwargs):
+    return ResNet(18, **kwargs)
+
+
+def resnet34(**kwargs):
+    return ResNet(34, **kwargs)
+
+
 def resnet50(**kwargs):
     return ResNet(50, **kwargs)
 
@@ -570,7 +632,7 @@ def resnet152(**kwargs):
     return ResNet(152, **kwargs)
 
 
-_factory = {"resnet50": resnet50, "resnet101": resnet101, "resnet152": resnet152}
+_factory = {"resnet18": resnet18, "resnet34": resnet34, "resnet50": resnet50, "resnet101": resnet101, "resnet152": resnet152}
 
 
 def names():

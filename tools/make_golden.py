@@ -223,6 +223,53 @@ def embed_fixture_wide():
     return ok
 
 
+def embed_fixture_basic():
+    """Embedding golden of the BasicBlock backbones: the REAL reference model (reid.models.create('resnet18' | 'resnet34') +
+    reid.evaluators.extract_features) under the stub modules of import_reid(), loaded with the build's seeded synthetic weights
+    (strictly: no key may be missing or unexpected, which pins names and shapes), on 4 seeded 256x128 images ->
+    tests/golden/embed_basic_ref.npz, and tests/basic_ref.py checked against it."""
+    import torch
+    import ssg_amd
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import basic_ref
+    reid = import_reid()
+    torch.manual_seed(0)
+    ok = True
+    rec = {}
+    g = torch.Generator().manual_seed(1)
+    imgs = torch.randn(4, 3, 256, 128, generator=g)
+    names = ["f%d" % i for i in range(4)]
+    loader = [(imgs, names, [0, 1, 2, 3], [0, 0, 0, 0])]
+    for depth, S in ((18, 2), (18, 1), (34, 2)):
+        model = reid.models.create('resnet%d' % depth, num_classes=0, num_split=S, cluster=False)
+        sd = ssg_amd.synthetic_state_dict(seed=1, depth=depth)
+        res = model.load_state_dict(sd, strict=False)
+        assert not res.unexpected_keys and not res.missing_keys, res
+        model.eval()
+        feats, _ = reid.evaluators.extract_features(model, loader, for_eval=False)
+        if S > 1:
+            ref = torch.stack([torch.stack(feats[f]) for f in names], 1)                  # [S+1, 4, 512]
+        else:
+            ref = torch.stack([feats[f] for f in names]).unsqueeze(0)
+        mine = torch.stack(basic_ref.embed_with_flip(sd, imgs, depth, S))
+        err = (ref - mine).abs().max().item()
+        print("embed resnet%d S=%d: torch-restatement vs reference max|diff| = %.3e  (feature |max| %.3e)" % (depth, S, err, ref.abs().max().item()))
+        ok = ok and err < 1e-6
+        rec["feats_r%d_S%d" % (depth, S)] = ref.numpy()
+        if (depth, S) == (18, 2):         # one plain model(x, for_eval=True) pair
+            with torch.no_grad():
+                x1, x2 = model(imgs, for_eval=True)
+            m1, m2 = basic_ref.forward(sd, imgs, depth, S, for_eval=True)
+            err = max((x1 - m1).abs().max().item(), (x2 - m2).abs().max().item())
+            print("model(x, for_eval=True) resnet18 S=2: restatement vs reference max|diff| = %.3e" % err)
+            ok = ok and err < 1e-6
+            rec["x1_r18_S2_eval"] = x1.numpy(); rec["x2_r18_S2_eval"] = x2.numpy()
+        if S == 2:
+            rec["keys_r%d" % depth] = np.array(["%s %s" % (k, "x".join(str(d) for d in v.shape)) for k, v in model.state_dict().items()])
+    np.savez_compressed(os.path.join(OUT, "embed_basic_ref.npz"), image_seed=1, weight_seed=1, **rec)
+    return ok
+
+
 def eval_fixture():
     """Retrieval metrics (reid/evaluators.py:88-129 evaluate_all -> reid/evaluation_metrics/ranking.py cmc, mean_ap with
     sklearn's average_precision_score): random query x gallery float32 distance blocks with Market-like id / camera
@@ -642,6 +689,10 @@ def main():
         ok = embed_fixture_wide()
         print("ALL OK" if ok else "ORACLE MISMATCH")
         sys.exit(0 if ok else 1)
+    if "--only-embed-basic" in sys.argv:  # regenerate just tests/golden/embed_basic_ref.npz
+        ok = embed_fixture_basic()
+        print("ALL OK" if ok else "ORACLE MISMATCH")
+        sys.exit(0 if ok else 1)
     if "--only-eval" in sys.argv:         # regenerate just tests/golden/eval_cases.npz
         ok = eval_fixture()
         print("ALL OK" if ok else "ORACLE MISMATCH")
@@ -767,6 +818,7 @@ def main():
 
     ok = init_fixture(mod) and ok
     ok = embed_fixture() and ok
+    ok = embed_fixture_basic() and ok
     ok = embed_fixture_wide() and ok
     ok = eval_fixture() and ok
     ok = pairwise_fixture() and ok
