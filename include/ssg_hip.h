@@ -590,6 +590,32 @@ int ssg_dec_kl_loss_grad_f32(const float* q, int B, int K, const float* gloss, f
 int ssg_dec_assign_grad_f32(const float* x, int64_t ldx, const float* c, const float* ns, const float* gq, int B, int K, int D, double alpha,
                             double* gns, float* gx, float* gc, ssg_stream_t stream);
 
+/* ---- train-mode batch normalisation with fused ReLU and residual add (fine-tune phase; csrc/batchnorm.hip) ----------------------
+ * float32 tensors of N x C x HW values, every channel sum and the per-element arithmetic in float64, no float atomics (the same call
+ * gives the same bits), no host read.  channels_last = 0: NCHW contiguous (C <= 65535 when HW > 1); 1: the channel is contiguous
+ * ([N, HW, C]: torch's channels_last; BatchNorm1d's [B, C] is HW = 1 in either).  N * HW >= 2 values per channel, fewer than 2^31
+ * elements.  Bad arguments are refused (-1) before any launch.
+ * ssg_bn_num_partials(): workgroups (partial sums) per channel of the two reductions, a function of the shape alone (-1: bad shape);
+ * ws: ssg_bn_workspace_bytes() bytes, 8-byte aligned, for those partials (0: bad shape). */
+int ssg_bn_num_partials(int N, int C, int HW, int channels_last);
+size_t ssg_bn_workspace_bytes(int N, int C, int HW, int channels_last);
+/* Forward statistics.  stat [3, C] float64 = {mean, biased variance, invstd = 1 / sqrt(var + eps)}.  running_mean / running_var [C]
+ * (NULL: left out) are updated in place: r = (1 - f) r + f v with v = mean, var * n / (n - 1); f = momentum, or 1 / num_batches_tracked[0]
+ * (device int64 that already counts this batch) when momentum < 0.  2 launches. */
+int ssg_bn_stats_f32(const float* x, int N, int C, int HW, int channels_last, double eps, double momentum, const int64_t* num_batches_tracked,
+                     float* running_mean, float* running_var, double* stat, void* ws, size_t ws_bytes, ssg_stream_t stream);
+/* y = (x - mean) * invstd * weight + bias  [+ residual, NULL: none]  [max(., 0) when relu != 0], rounded to float32 once.  1 launch. */
+int ssg_bn_apply_f32(const float* x, const double* stat, const float* weight, const float* bias, const float* residual, int relu, int N, int C,
+                     int HW, int channels_last, float* y, ssg_stream_t stream);
+/* Backward sums.  g = dy, or with y != NULL (the saved output of a forward with relu) g = dy where y > 0 and 0 elsewhere.
+ * dbias [C] = sum g, dweight [C] = sum g xh with xh = (x - mean) * invstd (either may be NULL); coef [2, C] float64 = {sum g / n,
+ * sum g xh / n}, the input of ssg_bn_backward_apply_f32.  2 launches. */
+int ssg_bn_backward_reduce_f32(const float* dy, const float* x, const float* y, const double* stat, int N, int C, int HW, int channels_last,
+                               double* coef, float* dweight, float* dbias, void* ws, size_t ws_bytes, ssg_stream_t stream);
+/* dx = (g - coef[0] - xh coef[1]) * invstd * weight; dresidual (NULL: none) = g.  1 launch. */
+int ssg_bn_backward_apply_f32(const float* dy, const float* x, const float* y, const double* stat, const float* weight, const double* coef, int N,
+                              int C, int HW, int channels_last, float* dx, float* dresidual, ssg_stream_t stream);
+
 /* ---- verification metrics (reid/evaluation_metrics/eval_far_gar.py:61-202; csrc/verify.hip) ------------------------------
  * D [m, n] float32 SQUARED distances at row pitch ld >= n (elements; m * ld * 4 may exceed 2^32), qlab int32 [m], rlab int32 [n], all on
  * the device and only read.  Element (i, j) is intra when rlab[j] == qlab[i], else inter (no camera filter); every element is taken as

@@ -61,6 +61,9 @@ def __getattr__(name):   # lazy: torch import only when the compute surface is t
     if name in ("ClusterAssignment", "target_distribution", "kl_loss", "use_device_assignment", "soft_assignment"):
         from . import dce
         return getattr(dce, name)
+    if name in ("batch_norm_train", "BatchNorm1d", "BatchNorm2d", "use_device_batchnorm"):
+        from . import batchnorm
+        return getattr(batchnorm, name)
     if name in ("DECFinedTrainer2Mixin", "DECJointTrainer2Mixin"):
         from . import trainers
         return getattr(trainers, name)
