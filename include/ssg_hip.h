@@ -642,6 +642,26 @@ int ssg_verify_count_f32(const float* D, int m, int n, size_t ld, const int32_t*
 /* s[i] = the value the three passes take for a stored d[i] (parity suite: equals numpy's float32 sqrt bit for bit). */
 int ssg_selftest_verify_sqrt(const float* d, int n, float* s, ssg_stream_t stream);
 
+/* ---- train-mode Conv2d (fine-tune phase; csrc/conv_train.hip) ----------------------------------------------------------------------
+ * Class: groups 1, dilation 1, no bias, stride 1, 1x1 with pad 0 or 3x3 with pad 1, Cin % 64 == 0, Cout % 64 == 0; float32 NHWC.
+ * Forward and data gradient are ssg_conv2d_nhwc_f32 (zero bias, no residual, no ReLU) on the two packings written here:
+ *   y [B,H,W,Cout] = conv(x, w_fwd),  dX [B,H,W,Cin] = conv(dY, w_dgrad) with Cin and Cout exchanged, same pad.
+ * ssg_conv_pack_train_f32: w is the [Cout,Cin,KH,KW] weight at element strides (s_co, s_ci, s_r, s_s), so a channels_last weight needs
+ * no copy.  w_fwd [Cout][KH*KW*Cin], k = ((ci/32)*KH*KW + r*KW + s)*32 + ci%32;  w_dgrad [Cin][KH*KW*Cout],
+ * k = ((co/32)*KH*KW + (KH-1-r)*KW + (KW-1-s))*32 + co%32.  Either output may be NULL (not both).  1 launch. */
+int ssg_conv_pack_train_f32(const float* w, int64_t s_co, int64_t s_ci, int64_t s_r, int64_t s_s, int Cout, int Cin, int KH, int KW,
+                            float* w_fwd, float* w_dgrad, ssg_stream_t stream);
+/* Weight gradient dW[co][ci][r][s] = sum over the M = B*H*W pixels of dY[m][co] * x[m shifted by the tap][ci] (zeros outside the image).
+ * The pixels are cut into ssg_conv_wgrad_num_slices() contiguous slices, a function of the shape alone (-1: bad shape); stage 1 writes
+ * one fp32 partial [Cout][KH*KW*Cin] per slice to ws (ssg_conv_wgrad_workspace_bytes() bytes; 0: bad shape), stage 2 adds the slices of
+ * every element in float64 in ascending order, rounds once and stores dw at element strides (s_co, s_ci, s_r, s_s).  No float atomics:
+ * the same call gives the same bits.  dy [B,H,W,Cout], x [B,H,W,Cin], 16-byte aligned.  stages: 3 = both (2 launches); 1 / 2 = stage 1 /
+ * stage 2 alone (timing).  Bad arguments are refused (-1) before any launch. */
+int ssg_conv_wgrad_num_slices(int M, int Cout, int KH, int KW, int Cin);
+size_t ssg_conv_wgrad_workspace_bytes(int M, int Cout, int KH, int KW, int Cin);
+int ssg_conv_wgrad_f32(const float* dy, const float* x, int B, int H, int W, int Cin, int Cout, int KH, int KW, float* dw, int64_t s_co,
+                       int64_t s_ci, int64_t s_r, int64_t s_s, void* ws, size_t ws_bytes, int stages, ssg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

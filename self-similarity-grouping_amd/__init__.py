@@ -64,6 +64,9 @@ def __getattr__(name):   # lazy: torch import only when the compute surface is t
     if name in ("batch_norm_train", "BatchNorm1d", "BatchNorm2d", "use_device_batchnorm"):
         from . import batchnorm
         return getattr(batchnorm, name)
+    if name in ("conv2d_train", "Conv2d", "use_device_conv"):
+        from . import conv
+        return getattr(conv, name)
     if name in ("DECFinedTrainer2Mixin", "DECJointTrainer2Mixin"):
         from . import trainers
         return getattr(trainers, name)
