@@ -662,6 +662,41 @@ size_t ssg_conv_wgrad_workspace_bytes(int M, int Cout, int KH, int KW, int Cin);
 int ssg_conv_wgrad_f32(const float* dy, const float* x, int B, int H, int W, int Cin, int Cout, int KH, int KW, float* dw, int64_t s_co,
                        int64_t s_ci, int64_t s_r, int64_t s_s, void* ws, size_t ws_bytes, int stages, ssg_stream_t stream);
 
+/* ---- train-mode strided Conv2d, the 7x7 stem and MaxPool2d(3, 2, 1) (fine-tune phase; csrc/conv_strided.hip) ------------------------
+ * Classes, all stride 2, groups 1, dilation 1, no bias, float32 NHWC:
+ *   S     1x1 with pad 0 or 3x3 with pad 1, Cin % 64 == 0, Cout % 64 == 0
+ *   stem  7x7 with pad 3, Cin = 3, Cout = 64; x is [B,H,W,4] RGB0 pixels (ssg_nchw_to_nhwc4), no data gradient
+ * OH = (H + 2 pad - KH) / 2 + 1, OW likewise.  Forward: y [B,OH,OW,Cout] = ssg_conv2d_nhwc_f32(x, w_fwd, stride 2, zero bias, no
+ * residual, no ReLU), with Cin = 4 for the stem.  No float atomics anywhere: the same call gives the same bits.
+ * ssg_conv_pack_strided_f32: w is the [Cout,Cin,KH,KW] weight at element strides.  Class S: w_fwd [Cout][KH*KW*Cin] as
+ * ssg_conv_pack_train_f32 writes it, w_dgrad [KH*KW][Cout][Cin]; either may be NULL (not both); one launch each.  Stem: w_fwd [64][224],
+ * k = (r*7 + s)*4 + c, zero where c == 3 or k >= 196; w_dgrad must be NULL. */
+int ssg_conv_pack_strided_f32(const float* w, int64_t s_co, int64_t s_ci, int64_t s_r, int64_t s_s, int Cout, int Cin, int KH, int KW,
+                              float* w_fwd, float* w_dgrad, ssg_stream_t stream);
+/* Data gradient of class S: dX [B,H,W,Cin] from dY [B,OH,OW,Cout] and the w_dgrad above.  The input pixels are split into their four
+ * (h mod 2, w mod 2) classes; each is a dense fp32-MFMA GEMM over K = (its 0, 1, 2 or 4 taps) x Cout, so no zero of a zero-stuffed dY
+ * is multiplied.  Every element of dX is written exactly once, the zeros that no tap reaches included.  All pointers 16-byte aligned.
+ * The stem is refused (-1).  1 launch. */
+int ssg_conv_dgrad_strided_f32(const float* dy, const float* w_dgrad, float* dx, int B, int H, int W, int Cin, int Cout, int KH, int KW,
+                               int stride, ssg_stream_t stream);
+/* Weight gradient of class S and of the stem: ssg_conv_wgrad_f32's two stages with the x row of output pixel (b, oh, ow) and tap (r, s)
+ * at (oh*stride + r - pad, ow*stride + s - pad), zero outside the image.  M = B*OH*OW output pixels are cut into
+ * ssg_conv_wgrad_strided_num_slices() slices (-1: bad shape); ws holds one fp32 partial per slice
+ * (ssg_conv_wgrad_strided_workspace_bytes(); 0: bad shape; the stem's partial rows are 13 K tiles of 16 taps x RGB0 = 832 floats).
+ * dw [Cout,Cin,KH,KW] at element strides; the stem's padding channel is never stored.  dy [B,OH,OW,Cout], x [B,H,W,Cin] (stem:
+ * [B,H,W,4]), 16-byte aligned.  stages as in ssg_conv_wgrad_f32. */
+int ssg_conv_wgrad_strided_num_slices(int M, int Cout, int KH, int KW, int Cin, int stride);
+size_t ssg_conv_wgrad_strided_workspace_bytes(int M, int Cout, int KH, int KW, int Cin, int stride);
+int ssg_conv_wgrad_strided_f32(const float* dy, const float* x, int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, float* dw,
+                               int64_t s_co, int64_t s_ci, int64_t s_r, int64_t s_s, void* ws, size_t ws_bytes, int stages, ssg_stream_t stream);
+/* MaxPool2d(3, stride 2, padding 1) on NHWC for training, C % 4 == 0, B*H*W < 2^31.  _idx: out [B,OH,OW,C] and idx [B,OH,OW,C] bytes,
+ * the winner's tap r*3 + s by torch's CPU rule: the maximum starts at -inf on the window's first element inside the image and an
+ * element replaces it when `val > max || isnan(val)`, in row-major window order (first maximum; a NaN wins).  _bwd: dX [B,H,W,C] as a
+ * gather -- every input element adds, oh ascending then ow ascending, the dY of the at most 2 x 2 windows that hold it and whose
+ * winner it is, and is written exactly once.  in / out / dy / dx 16-byte, idx 4-byte aligned.  1 launch each. */
+int ssg_maxpool3x3s2_idx_nhwc(const float* in, float* out, uint8_t* idx, int B, int H, int W, int C, ssg_stream_t stream);
+int ssg_maxpool3x3s2_bwd_nhwc(const float* dy, const uint8_t* idx, float* dx, int B, int H, int W, int C, ssg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -67,6 +67,9 @@ def __getattr__(name):   # lazy: torch import only when the compute surface is t
     if name in ("conv2d_train", "Conv2d", "use_device_conv"):
         from . import conv
         return getattr(conv, name)
+    if name in ("conv2d_train_strided", "StridedConv2d", "max_pool2d_train", "MaxPool2d", "use_device_maxpool"):
+        from . import conv_strided
+        return getattr(conv_strided, name)
     if name in ("DECFinedTrainer2Mixin", "DECJointTrainer2Mixin"):
         from . import trainers
         return getattr(trainers, name)

@@ -15,7 +15,8 @@ and its slice cut depends on the shape alone, so a forward + backward gives the 
 
     y = conv2d_train(x, weight, stride=1, padding=0)
     Conv2d                          nn.Conv2d with that forward (train and eval: the convolution has no mode)
-    use_device_conv(model)          swaps every nn.Conv2d of the class in a built model
+    use_device_conv(model)          swaps every nn.Conv2d of the class in a built model (strided=True: also the stride-2 classes and
+                                    the 7x7 stem of ssg_amd/conv_strided.py)
 
 There is no CPU fallback: without a GPU the forward raises SSGError."""
 import torch
@@ -170,24 +171,43 @@ def _adopt(old):
     return new
 
 
-def use_device_conv(model):
+def _adopt_strided(old):
+    from .conv_strided import StridedConv2d
+    new = StridedConv2d(old.in_channels, old.out_channels, old.kernel_size, old.stride, old.padding, device="meta")
+    new._parameters["weight"] = old._parameters["weight"]
+    new.training = old.training
+    return new
+
+
+def use_device_conv(model, strided=False):
     """Replace every `nn.Conv2d` of the device class in `model` (also under nn.DataParallel: the walk goes through `.module`) by
     `ssg_amd.Conv2d`.  The Parameter objects are kept, so optimiser groups built before the call and the state-dict keys stay valid.
     The qualified names of the convolutions left alone (strided, 7x7, with a bias, ..., and other subclasses of nn.Conv2d) are listed
-    in `model._ssg_conv_skipped`.  Run the model on `channels_last` input (`model.to(memory_format=torch.channels_last)`) so that no
-    layout copy is made between the layers.  Returns the model."""
+    in `model._ssg_conv_skipped`.  `strided=True` also swaps the stride-2 1x1 / 3x3 convolutions and the 7x7 stem for
+    `ssg_amd.StridedConv2d` (ssg_amd/conv_strided.py), which leaves none of a ResNet's convolutions on the skipped list; a later call
+    without the keyword leaves those modules where they are and does not list them.  Run the model
+    on `channels_last` input (`model.to(memory_format=torch.channels_last)`) so that no layout copy is made between the layers.
+    Returns the model."""
     skipped = []
+    if strided:
+        from .conv_strided import strided_unsupported_reason
+
+        def strided_ok(m):
+            return strided_unsupported_reason(m.in_channels, m.out_channels, m.kernel_size, m.stride, m.padding, m.dilation, m.groups,
+                                              m.bias is not None, m.padding_mode) is None
 
     def walk(parent, prefix):
         for name, child in list(parent._modules.items()):
             if child is None:
                 continue
             full = prefix + name
-            if isinstance(child, Conv2d):
+            if isinstance(child, Conv2d) or getattr(child, "_ssg_device_conv", False):     # already on the device path (either class)
                 continue
             if isinstance(child, nn.Conv2d):
                 if type(child) is nn.Conv2d and _module_reason(child) is None and child.weight.dtype == torch.float32:
                     parent._modules[name] = _adopt(child)
+                elif strided and type(child) is nn.Conv2d and strided_ok(child) and child.weight.dtype == torch.float32:
+                    parent._modules[name] = _adopt_strided(child)
                 else:
                     skipped.append(full)
                 continue

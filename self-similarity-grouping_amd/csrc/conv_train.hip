@@ -44,16 +44,23 @@ __global__ __launch_bounds__(256) void conv_pack_train_kernel(const float* __res
 
 // stage 1.  grid (K tiles = KH*KW*Cin/64, Cout / (64*CT), slices); 256 threads = 2 x 2 waves, wave (wr, wc) owns CT 32x32 tiles:
 // co rows (wr*CT + i)*32 .. +32, ci columns wc*32 .. +32 of the workgroup's tile.
-template <int CT>
+// MODE picks the x row of output pixel m and tap (r, s) -- the only thing the strided convolutions (csrc/conv_strided.hip) change:
+//   WG_UNIT   stride 1: the output pixel's own row shifted by the tap, H x W is both the input and the output size
+//   WG_STRIDE (oh*stride + r - pad, ow*stride + s - pad) of an H x W input; M counts the B*OH*OW output pixels
+//   WG_STEM   the same on RGB0 pixels (Cin = 4 in memory): the K tile is 16 taps x 4 channels, grid.x = ceil(KH*KW/16) tiles, the taps
+//             from KH*KW up are zero; ws rows are gridDim.x*64 long, k = tap*4 + c
+enum { WG_UNIT = 0, WG_STRIDE = 1, WG_STEM = 2 };
+template <int CT, int MODE = WG_UNIT>
 __global__ __launch_bounds__(256) void conv_wgrad_partial_kernel(const float* __restrict__ dy, const float* __restrict__ x, float* __restrict__ ws, int H,
-                                                                 int W, int Cin, int Cout, int KH, int KW, int pad, int M, int slice_len) {
+                                                                 int W, int Cin, int Cout, int KH, int KW, int pad, int M, int slice_len, int OH = 0,
+                                                                 int OW = 0, int stride = 1) {
   constexpr int CO_T = 64 * CT;                 // Cout tile
   constexpr int YV = CO_T / 4;                  // float4 per dY row of the tile
   __shared__ float4 ys[WG_PIX * YV];
   __shared__ float4 xs[WG_PIX * 16];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wr = wave >> 1, wc = wave & 1;
-  const int cchunks = Cin >> 6;
-  const int tap = blockIdx.x / cchunks, ci0 = (blockIdx.x % cchunks) << 6, co0 = blockIdx.y * CO_T;
+  const int cchunks = MODE == WG_STEM ? 1 : Cin >> 6;
+  const int tap = blockIdx.x / cchunks, ci0 = (blockIdx.x % cchunks) << 6, co0 = blockIdx.y * CO_T;      // WG_STEM: tap = the tile of 16 taps
   const int dr = tap / KW - pad, ds = tap % KW - pad;
   const int64_t m_begin = (int64_t)blockIdx.z * slice_len;
   const int64_t m_end = m_begin + slice_len < (int64_t)M ? m_begin + slice_len : (int64_t)M;
@@ -72,11 +79,22 @@ __global__ __launch_bounds__(256) void conv_wgrad_partial_kernel(const float* __
       const int f = tid + 256 * u, row = f >> 4, c4 = f & 15;
       const int64_t m = m0 + row;
       xr[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (m < m_end) {
-        const int ow = (int)(m % W), oh = (int)((m / W) % H);
-        const int ih = oh + dr, iw = ow + ds;
-        if (ih >= 0 && ih < H && iw >= 0 && iw < W)      // the tap stays inside the pixel's own image: m + dr*W + ds is in [0, M)
-          xr[u] = *reinterpret_cast<const float4*>(x + (m + (int64_t)dr * W + ds) * Cin + ci0 + c4 * 4);
+      if constexpr (MODE == WG_UNIT) {
+        if (m < m_end) {
+          const int ow = (int)(m % W), oh = (int)((m / W) % H);
+          const int ih = oh + dr, iw = ow + ds;
+          if (ih >= 0 && ih < H && iw >= 0 && iw < W)      // the tap stays inside the pixel's own image: m + dr*W + ds is in [0, M)
+            xr[u] = *reinterpret_cast<const float4*>(x + (m + (int64_t)dr * W + ds) * Cin + ci0 + c4 * 4);
+        }
+      } else if (m < m_end) {
+        const int ow = (int)(m % OW), oh = (int)((m / OW) % OH);
+        const int64_t b = m / ((int64_t)OW * OH);
+        const int t = MODE == WG_STEM ? tap * 16 + c4 : tap;                 // WG_STEM: this float4 is one tap's RGB0 pixel
+        const int ih = oh * stride + t / KW - pad, iw = ow * stride + t % KW - pad;
+        if (t < KH * KW && ih >= 0 && ih < H && iw >= 0 && iw < W) {         // inside image b: the row index is in [0, B*H*W)
+          const int64_t row = (b * H + ih) * W + iw;
+          xr[u] = *reinterpret_cast<const float4*>(MODE == WG_STEM ? x + row * 4 : x + row * Cin + ci0 + c4 * 4);
+        }
       }
     }
   };
@@ -111,8 +129,8 @@ __global__ __launch_bounds__(256) void conv_wgrad_partial_kernel(const float* __
     __syncthreads();
   }
 
-  const int64_t Ktot = (int64_t)KH * KW * Cin;
-  float* out = ws + (int64_t)blockIdx.z * Cout * Ktot + (int64_t)tap * Cin + ci0 + wc * 32 + l31;
+  const int64_t Ktot = MODE == WG_STEM ? (int64_t)gridDim.x * 64 : (int64_t)KH * KW * Cin;
+  float* out = ws + (int64_t)blockIdx.z * Cout * Ktot + (MODE == WG_STEM ? (int64_t)tap * 64 : (int64_t)tap * Cin + ci0) + wc * 32 + l31;
 #pragma unroll
   for (int i = 0; i < CT; i++)
 #pragma unroll
@@ -152,10 +170,11 @@ int conv_train_check_shape(const char* fn, int64_t M, int Cout, int KH, int KW, 
   return SSG_OK;
 }
 
-WgradPlan wgrad_plan(int M, int Cout, int KH, int KW, int Cin) {
+// ktiles: K tiles of 64 columns (one tap x 64 input channels; the stem: 16 taps x RGB0)
+WgradPlan wgrad_plan_tiles(int M, int Cout, int ktiles) {
   WgradPlan p;
   p.ct = (Cout % 128 == 0) ? 2 : 1;
-  const int64_t tiles = (int64_t)(Cout / (64 * p.ct)) * (KH * KW * Cin / 64);
+  const int64_t tiles = (int64_t)(Cout / (64 * p.ct)) * ktiles;
   const int64_t want = (WG_TARGET + tiles - 1) / tiles;                    // >= 1
   int64_t len = ((int64_t)M + want - 1) / want;
   len = (len + WG_PIX - 1) / WG_PIX * WG_PIX;
@@ -164,6 +183,8 @@ WgradPlan wgrad_plan(int M, int Cout, int KH, int KW, int Cin) {
   p.slices = (int)(((int64_t)M + p.slice_len - 1) / p.slice_len);
   return p;
 }
+
+WgradPlan wgrad_plan(int M, int Cout, int KH, int KW, int Cin) { return wgrad_plan_tiles(M, Cout, KH * KW * Cin / 64); }
 
 }  // namespace
 

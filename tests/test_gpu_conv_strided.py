@@ -1,0 +1,335 @@
+"""GPU suite of the strided train-mode Conv2d and the 7x7 stem (csrc/conv_strided.hip, ssg_amd/conv_strided.py): every case once
+through `conv2d_train_strided` and once through the raw entry points, against torch's `F.conv2d` and its autograd in float64 on the
+CPU (tests/conv_strided_ref.py).
+
+Accuracy criterion, derived and not measured (the one of test_gpu_conv_train.py): every element of every output satisfies
+
+    |dev - ref64| <= (L + 2) * 2^-24 * A
+
+with L the length of that output's reduction (KH KW Cin for y, KH KW Cout for dX -- an upper bound for every parity class -- and
+B OH OW for dW) and A the same operator applied to |x|, |w|, |dY| in float64.
+
+Composition (use_device_conv(strided=True) + use_device_batchnorm on a stride-2 bottleneck): test_gpu_conv_train.py's criterion on the
+parameter gradients,
+
+    err(device) <= F_COMP * err(float32 CPU run of the same block) + 2^-24,   err(v) = max |v - ref64| / max |ref64|
+
+with F_COMP the next power of two above the largest ratio measured on the MI355X (profiles/conv_strided_errors.txt, written by
+tools/conv_strided_errors.py from `measure()` / `measure_composition()` below) and never more than 4: measured 1.67 (bn2.weight),
+so F_COMP = 2.  The block's data keep every ReLU input at least 2^-15 away from 0 in float64 (asserted before anything touches the
+device)."""
+import copy
+import os
+import sys
+from functools import lru_cache
+
+import pytest
+
+torch = pytest.importorskip("torch")
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import conv_strided_ref as ref  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+F_COMP = 2.0
+FLOOR = 2.0 ** -24
+CL = torch.channels_last
+OUTS = ("y", "dx", "dw")
+
+
+def _lib():
+    from ssg_amd import _lib as m
+    return m.lib()
+
+
+def _case(name):
+    """the (B, H, W, Cin, Cout, k, seed) of a named case; the multi-slice ones take the smallest B that gives three ragged slices"""
+    if name in ref.CASES:
+        return ref.CASES[name]
+    H, W, cin, cout, k, seed = ref.MULTI[name]
+    B = ref.multi_slice_batch(_lib(), H, W, cin, cout, k)
+    # a slice rule with a floor that hides stage 2 from this suite must be changed, not tested around
+    assert B is not None, "no B <= 64 gives ssg_conv_wgrad_strided_num_slices >= 3 with a ragged slice at %r" % (ref.MULTI[name],)
+    return (B, H, W, cin, cout, k, seed)
+
+
+ALL = tuple(ref.CASES) + tuple(ref.MULTI)
+
+
+def _outs(case):
+    return ("y", "dw") if case[5] == 7 else OUTS            # the stem has no data gradient
+
+
+def _nan(*shape):
+    return torch.full(shape, float("nan"), dtype=torch.float32, device="cuda")
+
+
+def _api(case, x_cl=True, w_cl=False, x_grad=True, w_grad=True):
+    """one forward + backward through ssg_amd.conv2d_train_strided -> {y, dx, dw} as the device returned them"""
+    import ssg_amd
+    d = ref.reference(*case)[0]
+    x_grad = x_grad and d["k"] != 7
+    x = d["x"].cuda()
+    x = (x.contiguous(memory_format=CL) if x_cl else x).requires_grad_(x_grad)
+    w = d["w"].cuda()
+    w = (w.contiguous(memory_format=CL) if w_cl else w).requires_grad_(w_grad)
+    y = ssg_amd.conv2d_train_strided(x, w, 2, d["pad"])
+    # autograd.grad, not .backward(): AccumulateGrad re-lays a gradient out in its leaf's strides, which would hide what the function returns
+    wrt = [t for t, need in ((x, x_grad), (w, w_grad)) if need]
+    grads = dict(zip([n for n, need in (("dx", x_grad), ("dw", w_grad)) if need], torch.autograd.grad(y, wrt, d["gy"].cuda())))
+    return dict(y=y.detach(), dx=grads.get("dx"), dw=grads.get("dw"))
+
+
+def _abi(case):
+    """the raw entry points -> {y, dx, dw} as NCHW-shaped CPU tensors; every output and the workspace start as NaN"""
+    from ssg_amd._lib import check, ptr, stream
+    L = _lib()
+    B, H, W, cin, cout, k, _ = case
+    stem = k == 7
+    OH, OW = ref.out_hw(H, W, k)
+    d = ref.reference(*case)[0]
+    gy = d["gy"].cuda().permute(0, 2, 3, 1).contiguous()
+    w = d["w"].cuda()
+    s = w.stride()
+    zeros = torch.zeros(max(cin, cout), dtype=torch.float32, device="cuda")
+    if stem:
+        x = _nan(B, H, W, 4)
+        check(L.ssg_nchw_to_nhwc4(ptr(d["x"].cuda().contiguous()), ptr(x), B, H, W, 0, stream()), "nhwc4")
+        wf, wd = _nan(cout, 224), None
+        # the stem has no data-gradient packing and no data gradient
+        assert L.ssg_conv_pack_strided_f32(ptr(w), s[0], s[1], s[2], s[3], cout, cin, k, k, ptr(wf), ptr(wf), stream()) == -1
+        assert L.ssg_conv_dgrad_strided_f32(ptr(gy), ptr(wf), ptr(x), B, H, W, cin, cout, k, k, 2, stream()) == -1
+    else:
+        x = d["x"].cuda().permute(0, 2, 3, 1).contiguous()
+        wf, wd = _nan(cout, k * k * cin), _nan(k * k, cout, cin)
+    check(L.ssg_conv_pack_strided_f32(ptr(w), s[0], s[1], s[2], s[3], cout, cin, k, k, ptr(wf), ptr(wd), stream()), "pack")
+    y, dw = _nan(B, OH, OW, cout), _nan(cout, cin, k, k)
+    check(L.ssg_conv2d_nhwc_f32(ptr(x), ptr(wf), ptr(zeros), None, ptr(y), B, H, W, 4 if stem else cin, cout, k, k, 2, k // 2, 0, stream()), "forward")
+    out = {}
+    if not stem:
+        dx = _nan(B, H, W, cin)
+        check(L.ssg_conv_dgrad_strided_f32(ptr(gy), ptr(wd), ptr(dx), B, H, W, cin, cout, k, k, 2, stream()), "dgrad")
+        out["dx"] = dx.permute(0, 3, 1, 2).cpu()
+    M = B * OH * OW
+    n = L.ssg_conv_wgrad_strided_num_slices(M, cout, k, k, cin, 2)
+    nws = L.ssg_conv_wgrad_strided_workspace_bytes(M, cout, k, k, cin, 2)
+    assert n >= 1 and nws == 4 * n * cout * (13 * 64 if stem else k * k * cin)
+    ws = _nan(nws // 4 + 64)                               # 64 floats of guard behind the workspace
+    s = dw.stride()
+    check(L.ssg_conv_wgrad_strided_f32(ptr(gy), ptr(x), B, H, W, cin, cout, k, k, 2, ptr(dw), s[0], s[1], s[2], s[3], ptr(ws), nws, 3, stream()), "wgrad")
+    torch.cuda.synchronize()
+    assert bool(torch.isnan(ws[nws // 4:]).all()) and not bool(torch.isnan(ws[:nws // 4]).any())     # all of the workspace, nothing past it
+    out.update(y=y.permute(0, 3, 1, 2).cpu(), dw=dw.cpu(), w_fwd=wf.cpu(), w_dgrad=None if stem else wd.cpu())
+    return out
+
+
+def _check(case, got, which=None):
+    _, r64, A, L = ref.reference(*case)
+    for o in which or _outs(case):
+        g = got[o].detach().cpu().double()
+        assert g.shape == r64[o].shape and bool(torch.isfinite(g).all()), o
+        err, lim = (g - r64[o]).abs(), ref.bound(L[o], A[o])
+        worst = float((err / lim.clamp_min(1e-300)).max())
+        print("%s %s: max |dev - ref64| = %.3g, worst err / bound = %.3g (L = %d)" % (case[:6], o, float(err.max()), worst, L[o]))
+        assert bool((err <= lim).all()), "%s: %s misses (L + 2) 2^-24 A by a factor of %.3g" % (case[:6], o, worst)
+
+
+@pytest.mark.parametrize("name", ALL)
+def test_conv2d_train_strided_against_float64(name):
+    case = _case(name)
+    got = _api(case)
+    _check(case, got)
+    assert got["y"].is_contiguous(memory_format=CL) and (case[5] == 7 or got["dx"].is_contiguous(memory_format=CL))
+
+
+@pytest.mark.parametrize("name", ALL)
+def test_entry_points_against_float64(name):
+    case = _case(name)
+    got = _abi(case)
+    _check(case, got)
+    B, H, W, cin, cout, k, _ = case
+    w = ref.reference(*case)[0]["w"]
+    if k == 7:                                              # the packings move bits: k = (r*7 + s)*4 + c, zero padding
+        want = torch.zeros(cout, 56, 4)
+        want[:, :49, :3] = w.permute(0, 2, 3, 1).reshape(cout, 49, 3)
+        assert torch.equal(got["w_fwd"], want.reshape(cout, 224))
+    else:
+        from conv_train_ref import pack_fwd
+        assert torch.equal(got["w_fwd"], pack_fwd(w))
+        assert torch.equal(got["w_dgrad"], w.permute(2, 3, 0, 1).reshape(k * k, cout, cin))
+    api = _api(case)
+    for o in _outs(case):                                   # the autograd function adds nothing of its own
+        assert torch.equal(api[o].cpu(), got[o]), o
+
+
+def test_1x1_even_sides_are_exact_zeros():
+    """what no tap of a stride-2 1x1 reaches -- the three empty parity classes, the last row and column of an even-sized input -- is
+    written, and as exactly 0.0, by both routes"""
+    case = ref.CASES["1x1_even"]
+    for dx in (_api(case)["dx"].cpu(), _abi(case)["dx"]):
+        live = torch.zeros(dx.shape[2:], dtype=torch.bool)
+        live[0::2, 0::2] = True
+        assert not bool(live[-1].any()) and not bool(live[:, -1].any())            # even sides: the last row and column are unreached
+        dead = dx[:, :, ~live]
+        assert bool((dead == 0).all()) and not bool(torch.signbit(dead).any())
+        assert bool((dx[:, :, live] != 0).any())
+
+
+def test_multi_slice_cases_have_a_real_slice_sum():
+    L = _lib()
+    for name in ref.MULTI:
+        B, H, W, cin, cout, k, _ = _case(name)
+        OH, OW = ref.out_hw(H, W, k)
+        assert B <= 64
+        n = L.ssg_conv_wgrad_strided_num_slices(B * OH * OW, cout, k, k, cin, 2)
+        assert n >= 3 and (B * OH * OW) % n != 0           # equal slices cannot cover M: the last one is shorter
+
+
+def test_layouts_give_the_same_bits():
+    for name, cl_stride, std_stride in (("3x3_cout192", (64 * 9, 1, 3 * 64, 64), (64 * 9, 9, 3, 1)), ("stem_odd", (147, 1, 21, 3), (147, 49, 7, 1))):
+        case = ref.CASES[name]
+        base = _api(case, x_cl=True, w_cl=False)
+        assert base["dw"].is_contiguous()
+        _check(case, base)
+        for x_cl, w_cl in [(False, False), (True, True), (False, True)]:
+            got = _api(case, x_cl=x_cl, w_cl=w_cl)
+            for o in _outs(case):
+                assert torch.equal(got[o], base[o]), (name, o, x_cl, w_cl)
+            assert got["dw"].stride() == (cl_stride if w_cl else std_stride)     # the stem's dW also with a channels_last weight
+
+
+def test_frozen_input_and_frozen_weight():
+    case = ref.CASES["3x3_odd"]
+    base = _api(case)
+    got = _api(case, x_grad=False)
+    assert got["dx"] is None and torch.equal(got["dw"], base["dw"]) and torch.equal(got["y"], base["y"])
+    got = _api(case, w_grad=False)
+    assert got["dw"] is None and torch.equal(got["dx"], base["dx"])
+
+
+def test_two_passes_are_bit_identical():
+    for name in tuple(ref.MULTI) + ("3x3_even", "1x1_odd"):
+        case = _case(name)
+        a, b = _api(case), _api(case)
+        for o in _outs(case):
+            assert torch.equal(a[o], b[o]), (name, o)
+    case = _case("multi_3x3")
+    a, b = _abi(case), _abi(case)
+    for o in OUTS:
+        assert torch.equal(a[o], b[o]), o
+
+
+def test_stem_refuses_a_data_gradient_and_modules_run():
+    import ssg_amd
+    d = ref.reference(*ref.CASES["stem_even"])[0]
+    with pytest.raises(ValueError, match="data gradient"):
+        ssg_amd.conv2d_train_strided(d["x"].cuda().requires_grad_(True), d["w"].cuda(), 2, 3)
+    m = ssg_amd.StridedConv2d(3, 64, 7, 2, 3).cuda()
+    with torch.no_grad():
+        m.weight.copy_(d["w"])
+    y = m(d["x"].cuda())
+    assert torch.equal(y, _api(ref.CASES["stem_even"])["y"])
+    with torch.no_grad():
+        assert torch.equal(m.eval()(d["x"].cuda()), y)
+    with pytest.raises(RuntimeError):                       # a double backward raises
+        d3 = ref.reference(*ref.CASES["3x3_odd"])[0]
+        x, w = d3["x"].cuda().requires_grad_(True), d3["w"].cuda().requires_grad_(True)
+        (gx,) = torch.autograd.grad(ssg_amd.conv2d_train_strided(x, w, 2, 1), x, d3["gy"].cuda(), create_graph=True)
+        gx.sum().backward()
+
+
+# ---- composition -----------------------------------------------------------------------------------------------------------------------
+
+COMP_SHAPE = (4, 256, 8, 4)
+COMP_MARGIN = 2.0 ** -15
+
+
+def _comp_margin(block, x):
+    b = copy.deepcopy(block).double().train()
+    seen = []
+    h = b.relu.register_forward_pre_hook(lambda mod, inp: seen.append(float(inp[0].detach().abs().min())))
+    b(x.double())
+    h.remove()
+    assert len(seen) == 3
+    return min(seen)
+
+
+@lru_cache(maxsize=None)
+def _comp_data():
+    """(block in float32 on the CPU, x, gy): the first seed whose ReLU inputs all stay COMP_MARGIN away from 0 in float64"""
+    for seed in range(500, 600):
+        torch.manual_seed(seed)
+        block = ref.Bottleneck(256, 128, 2, ref.downsample(256, 512, 2))
+        for m in block.modules():
+            if isinstance(m, torch.nn.BatchNorm2d):
+                torch.nn.init.uniform_(m.weight, 0.5, 1.5)
+                torch.nn.init.uniform_(m.bias, -0.5, 0.5)
+        g = torch.Generator().manual_seed(seed)
+        x = torch.randn(*COMP_SHAPE, generator=g)
+        gy = torch.randn(COMP_SHAPE[0], 512, COMP_SHAPE[2] // 2, COMP_SHAPE[3] // 2, generator=g)
+        if _comp_margin(block, x) >= COMP_MARGIN:
+            return block, x, gy
+    raise AssertionError("no seed keeps the ReLU inputs away from 0")
+
+
+def _comp_grads(b, x, gy):
+    b.train()
+    b.zero_grad()
+    b(x).backward(gy)
+    return {n: p.grad.detach().cpu().double() for n, p in b.named_parameters()}
+
+
+@lru_cache(maxsize=None)
+def _comp_refs():
+    block, x, gy = _comp_data()
+    assert _comp_margin(block, x) >= COMP_MARGIN           # before anything touches the device
+    g64 = _comp_grads(copy.deepcopy(block).double(), x.double(), gy.double())
+    g32 = _comp_grads(copy.deepcopy(block), x, gy)
+    return g64, g32
+
+
+def _comp_device():
+    import ssg_amd
+    block, x, gy = _comp_data()
+    b = copy.deepcopy(block).cuda()
+    ssg_amd.use_device_conv(b, strided=True)
+    ssg_amd.use_device_batchnorm(b)
+    assert b._ssg_conv_skipped == [] and b._ssg_bn_skipped == []
+    assert isinstance(b.conv1, ssg_amd.Conv2d) and isinstance(b.conv3, ssg_amd.Conv2d)
+    assert isinstance(b.conv2, ssg_amd.StridedConv2d) and isinstance(b.downsample[0], ssg_amd.StridedConv2d)
+    b = b.to(memory_format=CL)
+    return _comp_grads(b, x.cuda().contiguous(memory_format=CL), gy.cuda().contiguous(memory_format=CL))
+
+
+def _err(v, r):
+    return float((v - r).abs().max()) / float(r.abs().max())
+
+
+def measure_composition():
+    """[(parameter, err_dev, err_f32)] of the composed block's parameter gradients"""
+    g64, g32 = _comp_refs()
+    dev = _comp_device()
+    assert sorted(dev) == sorted(g64)
+    return [(n, _err(dev[n], g64[n]), _err(g32[n], g64[n])) for n in g64]
+
+
+def test_composition_with_device_batchnorm():
+    for n, e_dev, e_f32 in measure_composition():
+        print("%-22s err_dev %.3g  err_f32 %.3g  ratio %.3g" % (n, e_dev, e_f32, e_dev / e_f32 if e_f32 else float("inf")))
+        assert e_dev <= F_COMP * e_f32 + FLOOR, (n, e_dev, e_f32)
+
+
+def measure():
+    """[(case, path, output, max |dev - ref64|, max |f32 CPU - ref64|, worst err_dev / bound)] for tools/conv_strided_errors.py"""
+    rows = []
+    for name in ALL:
+        case = _case(name)
+        d, r64, A, L = ref.reference(*case)
+        f32 = ref.outputs(d["x"], d["w"], d["gy"], d["pad"], torch.float32)
+        for path, got in (("conv2d_train_strided", _api(case)), ("entry points", _abi(case))):
+            for o in _outs(case):
+                err = (got[o].detach().cpu().double() - r64[o]).abs()
+                rows.append((name, case[:6], path, o, float(err.max()), float((f32[o].double() - r64[o]).abs().max()),
+                             float((err / ref.bound(L[o], A[o]).clamp_min(1e-300)).max())))
+    return rows
