@@ -697,6 +697,30 @@ int ssg_conv_wgrad_strided_f32(const float* dy, const float* x, int B, int H, in
 int ssg_maxpool3x3s2_idx_nhwc(const float* in, float* out, uint8_t* idx, int B, int H, int W, int C, ssg_stream_t stream);
 int ssg_maxpool3x3s2_bwd_nhwc(const float* dy, const uint8_t* idx, float* dx, int B, int H, int W, int C, ssg_stream_t stream);
 
+/* ---- train-mode head: stripe pooling and Linear (fine-tune phase; reid/models/resnet.py:93-120; csrc/head_train.hip) -----------------
+ * Pool forward: ssg_gap_stripes above on the NHWC map -- one launch, out [nsets,B,C] with nsets = S + 1 when S = num_split > 1, else 1;
+ * set 0 the global average, set s = 1..S the average of rows [(s-1)*(H/S), s*(H/S)); with H % S != 0 the trailing rows are in no stripe.
+ * Pool backward: dX[b,y,x,c] = g[0][b][c] / (H W) + g[stripe(y)][b][c] / ((H/S) W), each term a float32 division, added in that order;
+ * g [nsets,B,C]; bit s of set_mask says that set s received a gradient -- an absent set counts as zero and its part of g is not read
+ * (g may be NULL when set_mask == 0).  Every element of dX [B,H,W,C] is written exactly once; rows in no stripe get the global term
+ * alone.  C % 4 == 0, 1 <= num_split <= min(H, 30), g and dx 16-byte aligned.  1 launch.  Bad arguments are refused (-1) before any
+ * launch. */
+int ssg_gap_stripes_bwd(const float* g, int set_mask, float* dx, int B, int H, int W, int C, int num_split, ssg_stream_t stream);
+/* Linear: x [B,K], w [N,K] contiguous (nn.Linear's own weight, read where it lies: no pack launch, no transposed copy), bias [N] or
+ * NULL; B >= 1, N >= 1, K % 32 == 0, B and N at most 65535 * 32; the ragged last tile in B and in N is masked, nothing is padded in
+ * memory.  Three fp32-MFMA GEMMs (v_mfma_f32_32x32x2_f32, one 32 x 32 output tile per workgroup):
+ *   ssg_linear_fwd_f32    y  [B,N] = x w^T (+ bias)                       reduction over K
+ *   ssg_linear_dgrad_f32  dx [B,K] = dy w                                 reduction over N
+ *   ssg_linear_wgrad_f32  dw [N,K] = dy^T x  and  db [N] = sum_b dy[b][n] reduction over B; dw or db may be NULL (not both; x may be
+ *                         NULL with dw).  db is summed in float64 in ascending b and rounded once (a second launch).
+ * No reduction is cut across workgroups, so there is no workspace: inside a workgroup wave w of 4 takes the reduction steps
+ * [128 t + 32 w, 128 t + 32 w + 32) of every stage t, and the four fp32 partial tiles are added per element in float64 in wave order
+ * (then the bias), rounded once.  The order is a function of the shape alone and there are no float atomics: the same call gives the
+ * same bits.  Bad arguments are refused (-1) before any launch. */
+int ssg_linear_fwd_f32(const float* x, const float* w, const float* bias, float* y, int B, int K, int N, ssg_stream_t stream);
+int ssg_linear_dgrad_f32(const float* dy, const float* w, float* dx, int B, int K, int N, ssg_stream_t stream);
+int ssg_linear_wgrad_f32(const float* dy, const float* x, float* dw, float* db, int B, int K, int N, ssg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -70,6 +70,9 @@ def __getattr__(name):   # lazy: torch import only when the compute surface is t
     if name in ("conv2d_train_strided", "StridedConv2d", "max_pool2d_train", "MaxPool2d", "use_device_maxpool"):
         from . import conv_strided
         return getattr(conv_strided, name)
+    if name in ("stripe_pool_train", "linear_train", "Linear", "DeviceHeadMixin", "use_device_head"):
+        from . import head
+        return getattr(head, name)
     if name in ("DECFinedTrainer2Mixin", "DECJointTrainer2Mixin"):
         from . import trainers
         return getattr(trainers, name)
