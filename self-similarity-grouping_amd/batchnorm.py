@@ -17,20 +17,14 @@ import torch
 from torch import nn
 from torch.autograd.function import once_differentiable
 
-from . import _lib
-from ._lib import SSGError, check, ptr, stream
+from . import _lib, _train
+from ._lib import check, ptr, stream
 
 __all__ = ["batch_norm_train", "BatchNorm1d", "BatchNorm2d", "use_device_batchnorm", "FUSE_DEFAULT"]
 
 # `use_device_batchnorm(model)` without `fuse=`: the fused block forward is the default only where it measured faster than the plain
 # swap by more than the spread of the repeated medians (profiles/batchnorm_times.txt, tools/time_batchnorm.py)
 FUSE_DEFAULT = False
-
-
-def _device():
-    if not torch.cuda.is_available():
-        raise SSGError("ssg_amd.batchnorm needs a GPU (there is no CPU fallback)")
-    return torch.device("cuda", torch.cuda.current_device())
 
 
 def _layout(t):
@@ -63,7 +57,7 @@ def _on(t, dev, dtype):
 class _BatchNormFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, residual, running, eps, relu):
-        dev = _device()
+        dev = _train.device("batchnorm")
         L = _lib.lib()
         xd, cl = _layout(x.detach().to(dev, torch.float32))
         N, C = xd.shape[0], xd.shape[1]
@@ -96,7 +90,7 @@ class _BatchNormFn(torch.autograd.Function):
         check(L.ssg_bn_apply_f32(ptr(xd), ptr(stat), ptr(w), ptr(b), ptr(r), int(bool(relu)), N, C, HW, cl, ptr(y), stream()), "ssg_bn_apply_f32")
         ctx.save_for_backward(xd, y if relu else None, w, stat)
         ctx.geom = (N, C, HW, cl, nws)
-        ctx.src = tuple(None if t is None else (t.device, t.dtype) for t in (x, weight, bias, residual))
+        ctx.src = _train.src(x, weight, bias, residual)
         return y
 
     @staticmethod
@@ -121,8 +115,7 @@ class _BatchNormFn(torch.autograd.Function):
             dr = torch.empty_like(xd) if need_r else None
             check(L.ssg_bn_backward_apply_f32(ptr(g), ptr(xd), ptr(y), ptr(stat), ptr(w), ptr(coef), N, C, HW, cl, ptr(dx), ptr(dr), stream()),
                   "ssg_bn_backward_apply_f32")
-        return (dx.to(device=sx[0], dtype=sx[1]) if need_x else None, dw.to(device=sw[0], dtype=sw[1]), db.to(device=sb[0], dtype=sb[1]),
-                dr.to(device=sr[0], dtype=sr[1]) if need_r else None, None, None, None)
+        return (_train.back(dx if need_x else None, sx), _train.back(dw, sw), _train.back(db, sb), _train.back(dr, sr), None, None, None)
 
 
 def _check_train_input(x, weight):
@@ -192,16 +185,13 @@ class BatchNorm1d(_DeviceBatchNorm, nn.BatchNorm1d):
         self._ssg_init(relu)
 
 
-def _adopt(old):
-    """the device module in place of `old`, holding the same Parameter and buffer objects"""
+def _swap(old):
+    """the device module in place of the plain `old`, holding the same Parameter and buffer objects; None when `old` is not affine
+    or does not track running statistics"""
+    if not (old.affine and old.track_running_stats):
+        return None
     cls = BatchNorm2d if isinstance(old, nn.BatchNorm2d) else BatchNorm1d
-    new = cls(old.num_features, old.eps, old.momentum)
-    for name in ("weight", "bias"):
-        new._parameters[name] = old._parameters[name]
-    for name in ("running_mean", "running_var", "num_batches_tracked"):
-        new._buffers[name] = old._buffers[name]
-    new.training = old.training
-    return new
+    return _train.adopt(cls(old.num_features, old.eps, old.momentum), old, ("weight", "bias"), ("running_mean", "running_var", "num_batches_tracked"))
 
 
 def _fused_bottleneck_forward(self, x):
@@ -271,35 +261,14 @@ def use_device_batchnorm(model, fuse=None):
     `base._modules` sees are unchanged).  Blocks of any other shape keep their forward and get the plain swap.  fuse=None: FUSE_DEFAULT.
     Returns the model."""
     fuse = FUSE_DEFAULT if fuse is None else bool(fuse)
-    skipped = []
 
-    def walk(parent, prefix):
-        for name, child in list(parent._modules.items()):
-            if child is None:
-                continue
-            full = prefix + name
-            if isinstance(child, _DeviceBatchNorm):
-                continue
-            if isinstance(child, nn.modules.batchnorm._BatchNorm):
-                if type(child) in (nn.BatchNorm1d, nn.BatchNorm2d) and child.affine and child.track_running_stats:
-                    parent._modules[name] = _adopt(child)
-                else:
-                    skipped.append(full)
-                continue
-            walk(child, full + ".")
-            if fuse:
-                kind = _block_kind(child)
-                if kind:
-                    _fuse_block(child, kind)
-                elif _is_stem_host(child):
-                    child._modules["bn1"].relu = True
-                    child._modules["relu"] = nn.Identity()
+    def fuse_one(m):
+        kind = _block_kind(m)
+        if kind:
+            _fuse_block(m, kind)
+        elif _is_stem_host(m):
+            m._modules["bn1"].relu = True
+            m._modules["relu"] = nn.Identity()
 
-    walk(model, "")
-    if fuse and _is_stem_host(model):
-        model._modules["bn1"].relu = True
-        model._modules["relu"] = nn.Identity()
-    elif fuse and _block_kind(model):
-        _fuse_block(model, _block_kind(model))
-    model._ssg_bn_skipped = skipped
-    return model
+    return _train.swap_modules(model, "_ssg_bn_skipped", nn.modules.batchnorm._BatchNorm, (nn.BatchNorm1d, nn.BatchNorm2d),
+                               lambda m: isinstance(m, _DeviceBatchNorm), _swap, fuse_one if fuse else None)

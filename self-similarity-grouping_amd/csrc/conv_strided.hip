@@ -18,7 +18,7 @@
 //   pool     the forward records the winner's tap (torch's CPU rule: `val > max || isnan(val)` in row-major window order), the
 //            backward gathers: an input element adds, oh ascending then ow ascending, the dY of the at most 2 x 2 windows that
 //            contain it and whose winner it is.
-#include "ssg_common.h"
+#include "train_common.h"
 
 namespace ssg {
 
@@ -91,7 +91,7 @@ __global__ __launch_bounds__(256) void conv_dgrad_s2_kernel(const float* __restr
     }
   };
 
-  wg_f32x16 acc;
+  f32x16 acc;
 #pragma unroll
   for (int e = 0; e < 16; e++) acc[e] = 0.f;
   const float* wsf = reinterpret_cast<const float*>(wsh);
@@ -198,26 +198,17 @@ __global__ __launch_bounds__(256) void maxpool3x3s2_bwd_kernel(const float* __re
 
 namespace {
 
-// 0: bad shape, 1: class S (1x1 pad 0 / 3x3 pad 1), 2: the stem
+// 0: bad shape, WG_STRIDE: class S (1x1 pad 0 / 3x3 pad 1), WG_STEM: the stem
 int conv_strided_class(const char* fn, int64_t M, int Cout, int KH, int KW, int Cin, int stride) {
   const bool k1 = (KH == 1 && KW == 1), k3 = (KH == 3 && KW == 3), k7 = (KH == 7 && KW == 7);
   if (M > 0 && M <= 0x7fffffffLL && stride == 2) {
-    if ((k1 || k3) && Cin > 0 && Cout > 0 && Cin % 64 == 0 && Cout % 64 == 0) return 1;
-    if (k7 && Cin == 3 && Cout == 64) return 2;
+    if ((k1 || k3) && Cin > 0 && Cout > 0 && Cin % 64 == 0 && Cout % 64 == 0) return WG_STRIDE;
+    if (k7 && Cin == 3 && Cout == 64) return WG_STEM;
   }
   ssg_set_error("%s: the strided train-mode convolution is stride 2 and either 1x1 (pad 0) or 3x3 (pad 1) with Cin %% 64 == 0, Cout %% 64 == 0, or the "
                 "7x7 (pad 3) stem 3 -> 64; 0 < pixels < 2^31 (M=%lld Cin=%d Cout=%d k=%dx%d stride=%d)", fn, (long long)M, Cin, Cout, KH, KW, stride);
   return 0;
 }
-
-constexpr int STEM_KTILES = 13;                         // ceil(49 / 16) K tiles of 16 taps x RGB0
-constexpr int STEM_KWS = STEM_KTILES * 64;              // workspace row of the stem: 208 taps x 4 channels
-
-WgradPlan wgrad_strided_plan(int cls, int M, int Cout, int KH, int KW, int Cin) {
-  return wgrad_plan_tiles(M, Cout, cls == 2 ? STEM_KTILES : KH * KW * Cin / 64);
-}
-
-size_t wgrad_strided_row(int cls, int KH, int KW, int Cin) { return cls == 2 ? (size_t)STEM_KWS : (size_t)KH * KW * Cin; }
 
 int pool_check(const char* fn, int B, int H, int W, int C) {
   if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || (C % 4) || (int64_t)B * H * W > 0x7fffffffLL) {
@@ -234,18 +225,17 @@ extern "C" int ssg_conv_pack_strided_f32(const float* w, int64_t s_co, int64_t s
   const char* fn = "ssg_conv_pack_strided_f32";
   const int cls = conv_strided_class(fn, 1, Cout, KH, KW, Cin, 2);
   if (!cls) return SSG_ERR_INVALID;
-  if (!w || (!w_fwd && !w_dgrad)) { ssg_set_error("%s: NULL pointer", fn); return SSG_ERR_INVALID; }
-  if (s_co < 0 || s_ci < 0 || s_r < 0 || s_s < 0) { ssg_set_error("%s: negative weight stride", fn); return SSG_ERR_INVALID; }
-  if (cls == 2 && w_dgrad) { ssg_set_error("%s: the stem has no data gradient (w_dgrad must be NULL)", fn); return SSG_ERR_INVALID; }
-  if (cls == 2) {
+  if (int rc = ssg_need_pointers(fn, w && (w_fwd || w_dgrad))) return rc;
+  if (int rc = ssg_need_weight_strides(fn, s_co, s_ci, s_r, s_s)) return rc;
+  if (cls == WG_STEM && w_dgrad) { ssg_set_error("%s: the stem has no data gradient (w_dgrad must be NULL)", fn); return SSG_ERR_INVALID; }
+  if (cls == WG_STEM) {
     if (!w_fwd) { ssg_set_error("%s: the stem has only a forward packing (w_fwd is NULL)", fn); return SSG_ERR_INVALID; }
     const int Kpad = 32 * ((KH * KW + 7) / 8);
     hipLaunchKernelGGL(conv_pack_stem_kernel, dim3((Cout * Kpad + 255) / 256), dim3(256), 0, stream, w, s_co, s_ci, s_r, s_s, Cout, KH, KW, Kpad, w_fwd);
     SSG_LAUNCH_CHECK("conv_pack_stem_kernel");
     return SSG_OK;
   }
-  const int64_t total = (int64_t)Cout * Cin * KH * KW;
-  const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
+  const int blocks = ssg_blocks256((int64_t)Cout * Cin * KH * KW, 4096);
   if (w_fwd) {
     hipLaunchKernelGGL(conv_pack_train_kernel, dim3(blocks), dim3(256), 0, stream, w, s_co, s_ci, s_r, s_s, Cout, Cin, KH, KW, w_fwd, (float*)nullptr);
     SSG_LAUNCH_CHECK("conv_pack_train_kernel");
@@ -263,9 +253,9 @@ extern "C" int ssg_conv_dgrad_strided_f32(const float* dy, const float* w_dgrad,
   if (B <= 0 || H <= 0 || W <= 0) { ssg_set_error("%s: empty input B=%d H=%d W=%d", fn, B, H, W); return SSG_ERR_INVALID; }
   const int cls = conv_strided_class(fn, (int64_t)B * H * W, Cout, KH, KW, Cin, stride);
   if (!cls) return SSG_ERR_INVALID;
-  if (cls == 2) { ssg_set_error("%s: the stem has no data gradient (the images do not require grad)", fn); return SSG_ERR_INVALID; }
-  if (!dy || !w_dgrad || !dx) { ssg_set_error("%s: NULL pointer", fn); return SSG_ERR_INVALID; }
-  if (((uintptr_t)dy & 15) || ((uintptr_t)w_dgrad & 15) || ((uintptr_t)dx & 15)) { ssg_set_error("%s: dy, w_dgrad and dx must be 16-byte aligned", fn); return SSG_ERR_INVALID; }
+  if (cls == WG_STEM) { ssg_set_error("%s: the stem has no data gradient (the images do not require grad)", fn); return SSG_ERR_INVALID; }
+  if (int rc = ssg_need_pointers(fn, dy && w_dgrad && dx)) return rc;
+  if (int rc = ssg_need_aligned16(fn, "dy, w_dgrad and dx", {dy, w_dgrad, dx})) return rc;
   const int pad = KH / 2, OH = (H + 2 * pad - KH) / 2 + 1, OW = (W + 2 * pad - KW) / 2 + 1;
   const int64_t m0 = (int64_t)B * ((H + 1) / 2) * ((W + 1) / 2);             // the (even, even) class is the largest
   const dim3 grid((unsigned)((m0 + DG_PX - 1) / DG_PX), Cin / 64, 4);
@@ -276,64 +266,32 @@ extern "C" int ssg_conv_dgrad_strided_f32(const float* dy, const float* w_dgrad,
 
 extern "C" int ssg_conv_wgrad_strided_num_slices(int M, int Cout, int KH, int KW, int Cin, int stride) {
   const int cls = conv_strided_class("ssg_conv_wgrad_strided_num_slices", M, Cout, KH, KW, Cin, stride);
-  return cls ? wgrad_strided_plan(cls, M, Cout, KH, KW, Cin).slices : SSG_ERR_INVALID;
+  return cls ? wgrad_plan(cls, M, Cout, KH, KW, Cin).slices : SSG_ERR_INVALID;
 }
 
 extern "C" size_t ssg_conv_wgrad_strided_workspace_bytes(int M, int Cout, int KH, int KW, int Cin, int stride) {
   const int cls = conv_strided_class("ssg_conv_wgrad_strided_workspace_bytes", M, Cout, KH, KW, Cin, stride);
-  return cls ? (size_t)wgrad_strided_plan(cls, M, Cout, KH, KW, Cin).slices * Cout * wgrad_strided_row(cls, KH, KW, Cin) * sizeof(float) : 0;
+  return cls ? wgrad_workspace_bytes(cls, M, Cout, KH, KW, Cin) : 0;
 }
 
 extern "C" int ssg_conv_wgrad_strided_f32(const float* dy, const float* x, int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, float* dw,
                                           int64_t s_co, int64_t s_ci, int64_t s_r, int64_t s_s, void* ws, size_t ws_bytes, int stages, hipStream_t stream) {
   const char* fn = "ssg_conv_wgrad_strided_f32";
-  if (stages < 1 || stages > 3) { ssg_set_error("%s: stages=%d (1: partial tiles, 2: slice sum, 3: both)", fn, stages); return SSG_ERR_INVALID; }
-  if (B <= 0 || H <= 0 || W <= 0) { ssg_set_error("%s: empty input B=%d H=%d W=%d", fn, B, H, W); return SSG_ERR_INVALID; }
+  if (int rc = wgrad_check_call(fn, stages, B, H, W)) return rc;
   if ((int64_t)B * H * W > 0x7fffffffLL) { ssg_set_error("%s: B*H*W = %lld is 2^31 or more", fn, (long long)B * H * W); return SSG_ERR_INVALID; }
   const int pad = KH / 2, OH = (H + 2 * pad - KH) / 2 + 1, OW = (W + 2 * pad - KW) / 2 + 1;     // stride 2 (checked next); OH, OW >= 1
   const int cls = conv_strided_class(fn, (int64_t)B * OH * OW, Cout, KH, KW, Cin, stride);
   if (!cls) return SSG_ERR_INVALID;
-  if (!dy || !x || !dw) { ssg_set_error("%s: NULL pointer", fn); return SSG_ERR_INVALID; }
-  if (((uintptr_t)dy & 15) || ((uintptr_t)x & 15)) { ssg_set_error("%s: dy and x must be 16-byte aligned", fn); return SSG_ERR_INVALID; }
-  if (s_co < 0 || s_ci < 0 || s_r < 0 || s_s < 0) { ssg_set_error("%s: negative weight stride", fn); return SSG_ERR_INVALID; }
-  const int M = B * OH * OW;
-  const WgradPlan p = wgrad_strided_plan(cls, M, Cout, KH, KW, Cin);
-  const size_t need = (size_t)p.slices * Cout * wgrad_strided_row(cls, KH, KW, Cin) * sizeof(float);
-  if (!ws || ws_bytes < need || ((uintptr_t)ws & 3)) {
-    ssg_set_error("%s: workspace of %zu bytes (4-byte aligned) needed, got %zu", fn, need, ws ? ws_bytes : (size_t)0);
-    return SSG_ERR_INVALID;
-  }
-  if (p.slices > 65535) { ssg_set_error("%s: %d slices", fn, p.slices); return SSG_ERR_INVALID; }
-  const dim3 grid(cls == 2 ? STEM_KTILES : KH * KW * Cin / 64, Cout / (64 * p.ct), p.slices);
-  if (!(stages & 1)) {
-  } else if (cls == 2)
-    hipLaunchKernelGGL((conv_wgrad_partial_kernel<1, WG_STEM>), grid, dim3(256), 0, stream, dy, x, (float*)ws, H, W, 4, Cout, KH, KW, pad, M, p.slice_len, OH, OW, 2);
-  else if (p.ct == 2)
-    hipLaunchKernelGGL((conv_wgrad_partial_kernel<2, WG_STRIDE>), grid, dim3(256), 0, stream, dy, x, (float*)ws, H, W, Cin, Cout, KH, KW, pad, M, p.slice_len, OH, OW, 2);
-  else
-    hipLaunchKernelGGL((conv_wgrad_partial_kernel<1, WG_STRIDE>), grid, dim3(256), 0, stream, dy, x, (float*)ws, H, W, Cin, Cout, KH, KW, pad, M, p.slice_len, OH, OW, 2);
-  SSG_LAUNCH_CHECK("conv_wgrad_partial_kernel (strided)");
-  if (!(stages & 2)) {
-  } else if (cls == 2) {
-    hipLaunchKernelGGL(conv_wgrad_reduce_stem_kernel, dim3((Cout * KH * KW * 3 + 255) / 256), dim3(256), 0, stream, (const float*)ws, p.slices, Cout, KH, KW,
-                       STEM_KWS, dw, s_co, s_ci, s_r, s_s);
-  } else {
-    const int64_t total = (int64_t)Cout * KH * KW * Cin;
-    const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-    hipLaunchKernelGGL(conv_wgrad_reduce_kernel, dim3(blocks), dim3(256), 0, stream, (const float*)ws, p.slices, Cout, Cin, KH, KW, dw, s_co, s_ci, s_r, s_s);
-  }
-  SSG_LAUNCH_CHECK("conv_wgrad_reduce_kernel (strided)");
-  return SSG_OK;
+  return conv_wgrad_launch(fn, cls, dy, x, H, W, Cin, Cout, KH, KW, OH, OW, 2, B * OH * OW, dw, s_co, s_ci, s_r, s_s, ws, ws_bytes, stages, stream);
 }
 
 extern "C" int ssg_maxpool3x3s2_idx_nhwc(const float* in, float* out, uint8_t* idx, int B, int H, int W, int C, hipStream_t stream) {
   const char* fn = "ssg_maxpool3x3s2_idx_nhwc";
   if (int rc = pool_check(fn, B, H, W, C)) return rc;
-  if (!in || !out || !idx) { ssg_set_error("%s: NULL pointer", fn); return SSG_ERR_INVALID; }
+  if (int rc = ssg_need_pointers(fn, in && out && idx)) return rc;
   if (((uintptr_t)in & 15) || ((uintptr_t)out & 15) || ((uintptr_t)idx & 3)) { ssg_set_error("%s: in / out must be 16-byte, idx 4-byte aligned", fn); return SSG_ERR_INVALID; }
   const int OH = (H - 1) / 2 + 1, OW = (W - 1) / 2 + 1;
-  const int64_t total = (int64_t)B * OH * OW * (C / 4);
-  const int blocks = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
+  const int blocks = ssg_blocks256((int64_t)B * OH * OW * (C / 4), 16384);
   hipLaunchKernelGGL(maxpool3x3s2_idx_kernel, dim3(blocks), dim3(256), 0, stream, in, out, idx, B, H, W, C, OH, OW);
   SSG_LAUNCH_CHECK("maxpool3x3s2_idx_kernel");
   return SSG_OK;
@@ -342,11 +300,10 @@ extern "C" int ssg_maxpool3x3s2_idx_nhwc(const float* in, float* out, uint8_t* i
 extern "C" int ssg_maxpool3x3s2_bwd_nhwc(const float* dy, const uint8_t* idx, float* dx, int B, int H, int W, int C, hipStream_t stream) {
   const char* fn = "ssg_maxpool3x3s2_bwd_nhwc";
   if (int rc = pool_check(fn, B, H, W, C)) return rc;
-  if (!dy || !idx || !dx) { ssg_set_error("%s: NULL pointer", fn); return SSG_ERR_INVALID; }
+  if (int rc = ssg_need_pointers(fn, dy && idx && dx)) return rc;
   if (((uintptr_t)dy & 15) || ((uintptr_t)dx & 15) || ((uintptr_t)idx & 3)) { ssg_set_error("%s: dy / dx must be 16-byte, idx 4-byte aligned", fn); return SSG_ERR_INVALID; }
   const int OH = (H - 1) / 2 + 1, OW = (W - 1) / 2 + 1;
-  const int64_t total = (int64_t)B * H * W * (C / 4);
-  const int blocks = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
+  const int blocks = ssg_blocks256((int64_t)B * H * W * (C / 4), 16384);
   hipLaunchKernelGGL(maxpool3x3s2_bwd_kernel, dim3(blocks), dim3(256), 0, stream, dy, idx, dx, B, H, W, C, OH, OW);
   SSG_LAUNCH_CHECK("maxpool3x3s2_bwd_kernel");
   return SSG_OK;

@@ -18,15 +18,13 @@
 //      contiguous in memory and in LDS, so no tile is transposed and every LDS read is 32 consecutive dwords.  The fp32 partial tile
 //      goes to ws [slice][Cout][KH*KW*Cin].
 //   2. every element adds its slices in float64 in ascending slice order, rounds once and is stored with the caller's strides.
-#include "ssg_common.h"
+#include "train_common.h"
 
 namespace ssg {
 
 constexpr int WG_PIX = 32;          // pixels per LDS stage
 constexpr int WG_MIN_SLICE = 256;   // pixels: below this a slice is not worth its workspace pass
 constexpr int WG_TARGET = 1024;     // workgroups wanted in stage 1 (4 per CU)
-
-typedef float wg_f32x16 __attribute__((ext_vector_type(16)));
 
 __global__ __launch_bounds__(256) void conv_pack_train_kernel(const float* __restrict__ w, int64_t s0, int64_t s1, int64_t s2, int64_t s3, int Cout,
                                                               int Cin, int KH, int KW, float* __restrict__ w_fwd, float* __restrict__ w_dgrad) {
@@ -99,7 +97,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_partial_kernel(const float* __
     }
   };
 
-  wg_f32x16 acc[CT];
+  f32x16 acc[CT];
 #pragma unroll
   for (int i = 0; i < CT; i++)
 #pragma unroll
@@ -152,6 +150,10 @@ __global__ __launch_bounds__(256) void conv_wgrad_reduce_kernel(const float* __r
   }
 }
 
+// stage 2 of the stem (csrc/conv_strided.hip, with the stem's other kernels)
+__global__ __launch_bounds__(256) void conv_wgrad_reduce_stem_kernel(const float* __restrict__ ws, int slices, int Cout, int KH, int KW, int Kws,
+                                                                     float* __restrict__ dw, int64_t s0, int64_t s1, int64_t s2, int64_t s3);
+
 }  // namespace ssg
 
 namespace {
@@ -170,11 +172,22 @@ int conv_train_check_shape(const char* fn, int64_t M, int Cout, int KH, int KW, 
   return SSG_OK;
 }
 
-// ktiles: K tiles of 64 columns (one tap x 64 input channels; the stem: 16 taps x RGB0)
-WgradPlan wgrad_plan_tiles(int M, int Cout, int ktiles) {
+constexpr int STEM_KTILES = 13;                         // ceil(49 / 16) K tiles of 16 taps x RGB0
+constexpr int STEM_KWS = STEM_KTILES * 64;              // workspace row of the stem: 208 taps x 4 channels
+
+// The functions below take the class of the convolution as the MODE of its stage 1 kernel (WG_UNIT, WG_STRIDE or WG_STEM), already
+// validated by the caller, and M = the B*OH*OW output pixels.
+
+// K tiles of 64 columns: one tap x 64 input channels; the stem: 16 taps x RGB0
+int wgrad_ktiles(int mode, int KH, int KW, int Cin) { return mode == WG_STEM ? STEM_KTILES : KH * KW * Cin / 64; }
+
+// floats of one workspace row
+size_t wgrad_row(int mode, int KH, int KW, int Cin) { return mode == WG_STEM ? (size_t)STEM_KWS : (size_t)KH * KW * Cin; }
+
+WgradPlan wgrad_plan(int mode, int M, int Cout, int KH, int KW, int Cin) {
   WgradPlan p;
   p.ct = (Cout % 128 == 0) ? 2 : 1;
-  const int64_t tiles = (int64_t)(Cout / (64 * p.ct)) * ktiles;
+  const int64_t tiles = (int64_t)(Cout / (64 * p.ct)) * wgrad_ktiles(mode, KH, KW, Cin);
   const int64_t want = (WG_TARGET + tiles - 1) / tiles;                    // >= 1
   int64_t len = ((int64_t)M + want - 1) / want;
   len = (len + WG_PIX - 1) / WG_PIX * WG_PIX;
@@ -184,28 +197,77 @@ WgradPlan wgrad_plan_tiles(int M, int Cout, int ktiles) {
   return p;
 }
 
-WgradPlan wgrad_plan(int M, int Cout, int KH, int KW, int Cin) { return wgrad_plan_tiles(M, Cout, KH * KW * Cin / 64); }
+size_t wgrad_workspace_bytes(int mode, int M, int Cout, int KH, int KW, int Cin) {
+  return (size_t)wgrad_plan(mode, M, Cout, KH, KW, Cin).slices * Cout * wgrad_row(mode, KH, KW, Cin) * sizeof(float);
+}
+
+// what both weight gradient entry points refuse first
+int wgrad_check_call(const char* fn, int stages, int B, int H, int W) {
+  if (stages < 1 || stages > 3) { ssg_set_error("%s: stages=%d (1: partial tiles, 2: slice sum, 3: both)", fn, stages); return SSG_ERR_INVALID; }
+  if (B <= 0 || H <= 0 || W <= 0) { ssg_set_error("%s: empty input B=%d H=%d W=%d", fn, B, H, W); return SSG_ERR_INVALID; }
+  return SSG_OK;
+}
+
+// The weight gradient of every class behind ssg_conv_wgrad_f32 and ssg_conv_wgrad_strided_f32 (csrc/conv_strided.hip): the pointer,
+// stride and workspace checks, the plan, stage 1 (CT x MODE) and the matching stage 2.  H x W is the input, OH x OW the output size.
+int conv_wgrad_launch(const char* fn, int mode, const float* dy, const float* x, int H, int W, int Cin, int Cout, int KH, int KW, int OH, int OW, int stride,
+                      int M, float* dw, int64_t s_co, int64_t s_ci, int64_t s_r, int64_t s_s, void* ws, size_t ws_bytes, int stages, hipStream_t stream) {
+  if (int rc = ssg_need_pointers(fn, dy && x && dw)) return rc;
+  if (int rc = ssg_need_aligned16(fn, "dy and x", {dy, x})) return rc;
+  if (int rc = ssg_need_weight_strides(fn, s_co, s_ci, s_r, s_s)) return rc;
+  const WgradPlan p = wgrad_plan(mode, M, Cout, KH, KW, Cin);
+  const size_t need = wgrad_workspace_bytes(mode, M, Cout, KH, KW, Cin);
+  if (!ws || ws_bytes < need || ((uintptr_t)ws & 3)) {
+    ssg_set_error("%s: workspace of %zu bytes (4-byte aligned) needed, got %zu", fn, need, ws ? ws_bytes : (size_t)0);
+    return SSG_ERR_INVALID;
+  }
+  if (p.slices > 65535) { ssg_set_error("%s: %d slices", fn, p.slices); return SSG_ERR_INVALID; }
+  const int pad = KH / 2, cin_mem = mode == WG_STEM ? 4 : Cin;             // the stem reads RGB0 pixels
+  const dim3 grid(wgrad_ktiles(mode, KH, KW, Cin), Cout / (64 * p.ct), p.slices);
+#define SSG_WG_PARTIAL(CT, MODE)                                                                                                                \
+  hipLaunchKernelGGL((conv_wgrad_partial_kernel<CT, MODE>), grid, dim3(256), 0, stream, dy, x, (float*)ws, H, W, cin_mem, Cout, KH, KW, pad, M, \
+                     p.slice_len, OH, OW, stride)
+  if (!(stages & 1)) {
+  } else if (mode == WG_UNIT) {
+    if (p.ct == 2) SSG_WG_PARTIAL(2, WG_UNIT); else SSG_WG_PARTIAL(1, WG_UNIT);
+  } else if (mode == WG_STEM) {
+    SSG_WG_PARTIAL(1, WG_STEM);
+  } else {
+    if (p.ct == 2) SSG_WG_PARTIAL(2, WG_STRIDE); else SSG_WG_PARTIAL(1, WG_STRIDE);
+  }
+#undef SSG_WG_PARTIAL
+  SSG_LAUNCH_CHECK(mode == WG_UNIT ? "conv_wgrad_partial_kernel" : "conv_wgrad_partial_kernel (strided)");
+  if (!(stages & 2)) {
+  } else if (mode == WG_STEM) {
+    hipLaunchKernelGGL(conv_wgrad_reduce_stem_kernel, dim3((Cout * KH * KW * 3 + 255) / 256), dim3(256), 0, stream, (const float*)ws, p.slices, Cout, KH, KW,
+                       STEM_KWS, dw, s_co, s_ci, s_r, s_s);
+  } else {
+    hipLaunchKernelGGL(conv_wgrad_reduce_kernel, dim3(ssg_blocks256((int64_t)Cout * KH * KW * Cin, 8192)), dim3(256), 0, stream, (const float*)ws, p.slices,
+                       Cout, Cin, KH, KW, dw, s_co, s_ci, s_r, s_s);
+  }
+  SSG_LAUNCH_CHECK(mode == WG_UNIT ? "conv_wgrad_reduce_kernel" : "conv_wgrad_reduce_kernel (strided)");
+  return SSG_OK;
+}
 
 }  // namespace
 
 extern "C" int ssg_conv_wgrad_num_slices(int M, int Cout, int KH, int KW, int Cin) {
   if (conv_train_check_shape("ssg_conv_wgrad_num_slices", M, Cout, KH, KW, Cin)) return SSG_ERR_INVALID;
-  return wgrad_plan(M, Cout, KH, KW, Cin).slices;
+  return wgrad_plan(WG_UNIT, M, Cout, KH, KW, Cin).slices;
 }
 
 extern "C" size_t ssg_conv_wgrad_workspace_bytes(int M, int Cout, int KH, int KW, int Cin) {
   if (conv_train_check_shape("ssg_conv_wgrad_workspace_bytes", M, Cout, KH, KW, Cin)) return 0;
-  return (size_t)wgrad_plan(M, Cout, KH, KW, Cin).slices * Cout * KH * KW * Cin * sizeof(float);
+  return wgrad_workspace_bytes(WG_UNIT, M, Cout, KH, KW, Cin);
 }
 
 extern "C" int ssg_conv_pack_train_f32(const float* w, int64_t s_co, int64_t s_ci, int64_t s_r, int64_t s_s, int Cout, int Cin, int KH, int KW,
                                        float* w_fwd, float* w_dgrad, hipStream_t stream) {
   const char* fn = "ssg_conv_pack_train_f32";
   if (int rc = conv_train_check_shape(fn, 1, Cout, KH, KW, Cin)) return rc;
-  if (!w || (!w_fwd && !w_dgrad)) { ssg_set_error("%s: NULL pointer", fn); return SSG_ERR_INVALID; }
-  if (s_co < 0 || s_ci < 0 || s_r < 0 || s_s < 0) { ssg_set_error("%s: negative weight stride", fn); return SSG_ERR_INVALID; }
-  const int64_t total = (int64_t)Cout * Cin * KH * KW;
-  const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
+  if (int rc = ssg_need_pointers(fn, w && (w_fwd || w_dgrad))) return rc;
+  if (int rc = ssg_need_weight_strides(fn, s_co, s_ci, s_r, s_s)) return rc;
+  const int blocks = ssg_blocks256((int64_t)Cout * Cin * KH * KW, 4096);
   hipLaunchKernelGGL(conv_pack_train_kernel, dim3(blocks), dim3(256), 0, stream, w, s_co, s_ci, s_r, s_s, Cout, Cin, KH, KW, w_fwd, w_dgrad);
   SSG_LAUNCH_CHECK("conv_pack_train_kernel");
   return SSG_OK;
@@ -214,32 +276,8 @@ extern "C" int ssg_conv_pack_train_f32(const float* w, int64_t s_co, int64_t s_c
 extern "C" int ssg_conv_wgrad_f32(const float* dy, const float* x, int B, int H, int W, int Cin, int Cout, int KH, int KW, float* dw, int64_t s_co,
                                   int64_t s_ci, int64_t s_r, int64_t s_s, void* ws, size_t ws_bytes, int stages, hipStream_t stream) {
   const char* fn = "ssg_conv_wgrad_f32";
-  if (stages < 1 || stages > 3) { ssg_set_error("%s: stages=%d (1: partial tiles, 2: slice sum, 3: both)", fn, stages); return SSG_ERR_INVALID; }
-  if (B <= 0 || H <= 0 || W <= 0) { ssg_set_error("%s: empty input B=%d H=%d W=%d", fn, B, H, W); return SSG_ERR_INVALID; }
-  const int64_t M64 = (int64_t)B * H * W;
-  if (int rc = conv_train_check_shape(fn, M64, Cout, KH, KW, Cin)) return rc;
-  if (!dy || !x || !dw) { ssg_set_error("%s: NULL pointer", fn); return SSG_ERR_INVALID; }
-  if (((uintptr_t)dy & 15) || ((uintptr_t)x & 15)) { ssg_set_error("%s: dy and x must be 16-byte aligned", fn); return SSG_ERR_INVALID; }
-  if (s_co < 0 || s_ci < 0 || s_r < 0 || s_s < 0) { ssg_set_error("%s: negative weight stride", fn); return SSG_ERR_INVALID; }
-  const int M = (int)M64;
-  const WgradPlan p = wgrad_plan(M, Cout, KH, KW, Cin);
-  const size_t need = (size_t)p.slices * Cout * KH * KW * Cin * sizeof(float);
-  if (!ws || ws_bytes < need || ((uintptr_t)ws & 3)) {
-    ssg_set_error("%s: workspace of %zu bytes (4-byte aligned) needed, got %zu", fn, need, ws ? ws_bytes : (size_t)0);
-    return SSG_ERR_INVALID;
-  }
-  if (p.slices > 65535) { ssg_set_error("%s: %d slices", fn, p.slices); return SSG_ERR_INVALID; }
-  const int pad = KH / 2;
-  const dim3 grid(KH * KW * Cin / 64, Cout / (64 * p.ct), p.slices);
-  if (!(stages & 1)) {
-  } else if (p.ct == 2)
-    hipLaunchKernelGGL(conv_wgrad_partial_kernel<2>, grid, dim3(256), 0, stream, dy, x, (float*)ws, H, W, Cin, Cout, KH, KW, pad, M, p.slice_len);
-  else
-    hipLaunchKernelGGL(conv_wgrad_partial_kernel<1>, grid, dim3(256), 0, stream, dy, x, (float*)ws, H, W, Cin, Cout, KH, KW, pad, M, p.slice_len);
-  SSG_LAUNCH_CHECK("conv_wgrad_partial_kernel");
-  const int64_t total = (int64_t)Cout * KH * KW * Cin;
-  const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-  if (stages & 2) hipLaunchKernelGGL(conv_wgrad_reduce_kernel, dim3(blocks), dim3(256), 0, stream, (const float*)ws, p.slices, Cout, Cin, KH, KW, dw, s_co, s_ci, s_r, s_s);
-  SSG_LAUNCH_CHECK("conv_wgrad_reduce_kernel");
-  return SSG_OK;
+  if (int rc = wgrad_check_call(fn, stages, B, H, W)) return rc;
+  const int64_t M = (int64_t)B * H * W;                // stride 1 with pad KH / 2: the output has the input's size
+  if (int rc = conv_train_check_shape(fn, M, Cout, KH, KW, Cin)) return rc;
+  return conv_wgrad_launch(fn, WG_UNIT, dy, x, H, W, Cin, Cout, KH, KW, H, W, 1, (int)M, dw, s_co, s_ci, s_r, s_s, ws, ws_bytes, stages, stream);
 }

@@ -17,7 +17,7 @@
 // of every stage on v_mfma_f32_32x32x2_f32; the next stage's global loads fly under the MFMAs.  At the end the four waves' fp32 tiles
 // are added per element in float64 in wave order (+ bias), rounded once and stored with a mask.  The cut into four is fixed, so the
 // summation order is a function of the shape alone; there are no float atomics and no workspace.
-#include "ssg_common.h"
+#include "train_common.h"
 
 namespace ssg {
 
@@ -26,7 +26,6 @@ constexpr int LIN_RED = 128;         // reduction steps per LDS stage: 32 per wa
 constexpr int LIN_PITCH = 33;        // dwords per reduction step in LDS
 constexpr int LIN_LD = LIN_T * LIN_RED / 256;   // elements per thread, operand and stage
 
-typedef float lin_f32x16 __attribute__((ext_vector_type(16)));
 
 // element (out index o, reduction index r) of an operand lies at p[o * so + r * sr]; RC (reduction-contiguous) operands have sr == 1,
 // the others so == 1.  The thread -> element map of the global load follows the contiguous index so that a wave reads whole lines.
@@ -64,7 +63,7 @@ __global__ __launch_bounds__(256) void linear_gemm_kernel(const float* __restric
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, lk = lane >> 5;
   const int i0 = blockIdx.y * LIN_T, j0 = blockIdx.x * LIN_T;
   float av[LIN_LD], bv[LIN_LD];
-  lin_f32x16 acc;
+  f32x16 acc;
 #pragma unroll
   for (int e = 0; e < 16; e++) acc[e] = 0.f;
 
@@ -166,7 +165,7 @@ int lin_tiles(int n) { return (n + LIN_T - 1) / LIN_T; }
 extern "C" int ssg_linear_fwd_f32(const float* x, const float* w, const float* bias, float* y, int B, int K, int N, hipStream_t stream) {
   const char* fn = "ssg_linear_fwd_f32";
   if (int rc = linear_check(fn, B, K, N)) return rc;
-  if (!x || !w || !y) { ssg_set_error("%s: NULL pointer", fn); return SSG_ERR_INVALID; }
+  if (int rc = ssg_need_pointers(fn, x && w && y)) return rc;
   hipLaunchKernelGGL((linear_gemm_kernel<true, true>), dim3(lin_tiles(N), lin_tiles(B)), dim3(256), 0, stream, x, (int64_t)K, (int64_t)1, w, (int64_t)K, (int64_t)1,
                      bias, y, B, N, K);
   SSG_LAUNCH_CHECK("linear_gemm_kernel (forward)");
@@ -176,7 +175,7 @@ extern "C" int ssg_linear_fwd_f32(const float* x, const float* w, const float* b
 extern "C" int ssg_linear_dgrad_f32(const float* dy, const float* w, float* dx, int B, int K, int N, hipStream_t stream) {
   const char* fn = "ssg_linear_dgrad_f32";
   if (int rc = linear_check(fn, B, K, N)) return rc;
-  if (!dy || !w || !dx) { ssg_set_error("%s: NULL pointer", fn); return SSG_ERR_INVALID; }
+  if (int rc = ssg_need_pointers(fn, dy && w && dx)) return rc;
   hipLaunchKernelGGL((linear_gemm_kernel<true, false>), dim3(lin_tiles(K), lin_tiles(B)), dim3(256), 0, stream, dy, (int64_t)N, (int64_t)1, w, (int64_t)1, (int64_t)K,
                      (const float*)nullptr, dx, B, K, N);
   SSG_LAUNCH_CHECK("linear_gemm_kernel (data gradient)");
@@ -204,10 +203,9 @@ extern "C" int ssg_gap_stripes_bwd(const float* g, int set_mask, float* dx, int 
   }
   const int nsets = num_split > 1 ? num_split + 1 : 1;
   if (set_mask < 0 || (set_mask >> nsets)) { ssg_set_error("%s: set_mask %d names a set past the %d of num_split=%d", fn, set_mask, nsets, num_split); return SSG_ERR_INVALID; }
-  if (!dx || (set_mask && !g)) { ssg_set_error("%s: NULL pointer", fn); return SSG_ERR_INVALID; }
-  if (((uintptr_t)g & 15) || ((uintptr_t)dx & 15)) { ssg_set_error("%s: g and dx must be 16-byte aligned", fn); return SSG_ERR_INVALID; }
-  const int64_t total = (int64_t)B * H * W * (C >> 2);
-  const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
+  if (int rc = ssg_need_pointers(fn, dx && (g || !set_mask))) return rc;
+  if (int rc = ssg_need_aligned16(fn, "g and dx", {g, dx})) return rc;
+  const int blocks = ssg_blocks256((int64_t)B * H * W * (C >> 2), 8192);
   hipLaunchKernelGGL(gap_stripes_bwd_kernel, dim3(blocks), dim3(256), 0, stream, g, (unsigned)set_mask, dx, B, H, W, C, num_split);
   SSG_LAUNCH_CHECK("gap_stripes_bwd_kernel");
   return SSG_OK;

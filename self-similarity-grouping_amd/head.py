@@ -21,9 +21,9 @@ import torch
 from torch import nn
 from torch.autograd.function import once_differentiable
 
-from . import _lib
+from . import _lib, _train
 from ._lib import check, ptr, stream
-from .conv import CL, _device
+from .conv import CL
 
 __all__ = ["stripe_pool_train", "linear_train", "Linear", "DeviceHeadMixin", "use_device_head", "linear_unsupported_reason",
            "stripe_pool_unsupported_reason"]
@@ -53,14 +53,15 @@ def stripe_pool_unsupported_reason(shape, num_split):
 class _StripePoolFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, S):
-        dev = _device()
+        dev = _train.device("conv")
         xd = x.detach().to(dev, torch.float32).contiguous(memory_format=CL)
         B, C, h, w = xd.shape
         nsets = S + 1 if S > 1 else 1
         out = torch.empty((nsets, B, C), dtype=torch.float32, device=dev)
         check(_lib.lib().ssg_gap_stripes(ptr(xd), ptr(out), B, h, w, C, S, stream()), "ssg_gap_stripes")
         ctx.geom = (B, C, h, w, S)                    # nothing about x is kept but its shape
-        ctx.src = (x.device, x.dtype, dev)
+        ctx.src = _train.src(x)
+        ctx.dev = dev
         ctx.set_materialize_grads(False)              # a set that got no gradient arrives as None and is not read
         return tuple(out[i] for i in range(nsets))
 
@@ -68,7 +69,7 @@ class _StripePoolFn(torch.autograd.Function):
     @once_differentiable                              # a double backward raises
     def backward(ctx, *grads):
         B, C, h, w, S = ctx.geom
-        dev = ctx.src[2]
+        dev = ctx.dev
         g = torch.empty((len(grads), B, C), dtype=torch.float32, device=dev)
         mask = 0
         for i, gi in enumerate(grads):
@@ -77,7 +78,7 @@ class _StripePoolFn(torch.autograd.Function):
                 mask |= 1 << i
         dx = torch.empty((B, C, h, w), dtype=torch.float32, device=dev, memory_format=CL)
         check(_lib.lib().ssg_gap_stripes_bwd(ptr(g), mask, ptr(dx), B, h, w, C, S, stream()), "ssg_gap_stripes_bwd")
-        return dx.to(device=ctx.src[0], dtype=ctx.src[1]), None
+        return _train.back(dx, ctx.src[0]), None
 
 
 def stripe_pool_train(x, num_split=1):
@@ -90,8 +91,7 @@ def stripe_pool_train(x, num_split=1):
     why = stripe_pool_unsupported_reason(tuple(x.shape), num_split)
     if why is None and x.dtype != torch.float32:
         why = "x must be float32 (got %s)" % x.dtype
-    if why is not None:
-        raise ValueError("stripe_pool_train: " + why)
+    _train.refuse("stripe_pool_train", why)
     return _StripePoolFn.apply(x, int(num_split))
 
 
@@ -109,7 +109,7 @@ def linear_unsupported_reason(in_features, out_features):
 class _LinearFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias):
-        dev = _device()
+        dev = _train.device("conv")
         xd = x.detach().to(dev, torch.float32).contiguous()
         w = weight.detach().to(dev, torch.float32)
         b = None if bias is None else bias.detach().to(dev, torch.float32).contiguous()
@@ -117,7 +117,7 @@ class _LinearFn(torch.autograd.Function):
         y = torch.empty((B, N), dtype=torch.float32, device=dev)
         check(_lib.lib().ssg_linear_fwd_f32(ptr(xd), ptr(w), ptr(b), ptr(y), B, K, N, stream()), "ssg_linear_fwd_f32")
         ctx.save_for_backward(xd, w)                  # only x and the weight are kept
-        ctx.src = tuple(None if t is None else (t.device, t.dtype) for t in (x, weight, bias))
+        ctx.src = _train.src(x, weight, bias)
         return y
 
     @staticmethod
@@ -132,7 +132,6 @@ class _LinearFn(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             dx = torch.empty((B, K), dtype=torch.float32, device=dev)
             check(L.ssg_linear_dgrad_f32(ptr(g), ptr(w), ptr(dx), B, K, N, stream()), "ssg_linear_dgrad_f32")
-            dx = dx.to(device=ctx.src[0][0], dtype=ctx.src[0][1])
         want_db = ctx.src[2] is not None and ctx.needs_input_grad[2]
         if ctx.needs_input_grad[1] or want_db:
             if ctx.needs_input_grad[1]:
@@ -140,11 +139,7 @@ class _LinearFn(torch.autograd.Function):
             if want_db:
                 db = torch.empty((N,), dtype=torch.float32, device=dev)
             check(L.ssg_linear_wgrad_f32(ptr(g), ptr(xd), ptr(dw), ptr(db), B, K, N, stream()), "ssg_linear_wgrad_f32")
-            if dw is not None:
-                dw = dw.to(device=ctx.src[1][0], dtype=ctx.src[1][1])
-            if db is not None:
-                db = db.to(device=ctx.src[2][0], dtype=ctx.src[2][1])
-        return dx, dw, db
+        return tuple(_train.back(g, where) for g, where in zip((dx, dw, db), ctx.src))
 
 
 def linear_train(x, weight, bias=None):
@@ -167,8 +162,7 @@ def linear_train(x, weight, bias=None):
         why = "bias must be [N] = [%d] (got %r)" % (weight.shape[0], tuple(bias.shape))
     if why is None and any(t.dtype != torch.float32 for t in (x, weight, bias) if t is not None):
         why = "x, weight and bias must be float32 (got %s)" % ", ".join(str(t.dtype) for t in (x, weight, bias) if t is not None)
-    if why is not None:
-        raise ValueError("linear_train: " + why)
+    _train.refuse("linear_train", why)
     return _LinearFn.apply(x, weight, bias)
 
 
@@ -177,28 +171,20 @@ class Linear(nn.Linear):
     in train and in eval mode.  Only the device class (in_features % 32 == 0) can be built; the input is [B, in_features]."""
 
     def __init__(self, in_features, out_features, bias=True, **kw):
-        why = linear_unsupported_reason(in_features, out_features)
-        if why is not None:
-            raise ValueError("ssg_amd.Linear: " + why)
+        _train.refuse("ssg_amd.Linear", linear_unsupported_reason(in_features, out_features))
         super(Linear, self).__init__(in_features, out_features, bias, **kw)
 
     def forward(self, input):
         return linear_train(input, self.weight, self.bias)
 
 
-def _adopt(old):
-    """the device module in place of `old`, holding the same Parameter objects"""
-    new = Linear(old.in_features, old.out_features, old.bias is not None, device="meta")
-    new._parameters["weight"] = old._parameters["weight"]
-    new._parameters["bias"] = old._parameters["bias"]
-    new.training = old.training
-    return new
-
-
-def _swappable(m):
-    if type(m) is not nn.Linear or linear_unsupported_reason(m.in_features, m.out_features) is not None:
-        return False
-    return all(p.dtype == torch.float32 for p in (m.weight, m.bias) if p is not None) and m.weight.is_contiguous()
+def _swap(m):
+    """the device module holding the Parameter objects of the plain nn.Linear `m`, None when `m` is outside the device class"""
+    if linear_unsupported_reason(m.in_features, m.out_features) is not None:
+        return None
+    if not (all(p.dtype == torch.float32 for p in (m.weight, m.bias) if p is not None) and m.weight.is_contiguous()):
+        return None
+    return _train.adopt(Linear(m.in_features, m.out_features, m.bias is not None, device="meta"), m, ("weight", "bias"))
 
 
 # ---- the model's forward ------------------------------------------------------------------------------------------------------------------
@@ -244,22 +230,7 @@ def use_device_head(model):
         if not hasattr(host, a):
             raise ValueError("use_device_head: the model has no attribute `%s` (it needs %s, as reid/models/resnet.py's ResNet has them)"
                              % (a, ", ".join(HEAD_ATTRIBUTES)))
-    skipped = []
-
-    def walk(parent, prefix):
-        for name, child in list(parent._modules.items()):
-            if child is None or isinstance(child, Linear):
-                continue
-            if isinstance(child, nn.Linear):
-                if _swappable(child):
-                    parent._modules[name] = _adopt(child)
-                else:
-                    skipped.append(prefix + name)
-                continue
-            walk(child, prefix + name + ".")
-
-    walk(model, "")
-    model._ssg_linear_skipped = skipped
+    _train.swap_modules(model, "_ssg_linear_skipped", nn.Linear, (nn.Linear,), lambda m: isinstance(m, Linear), _swap)
     if not isinstance(host, DeviceHeadMixin):
         cls = type(host)
         if cls not in _HEAD_CLASSES:

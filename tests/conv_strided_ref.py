@@ -6,7 +6,8 @@ from functools import lru_cache
 import torch
 import torch.nn.functional as Fn
 
-from conv_train_ref import U, Bottleneck, bound, downsample  # noqa: F401
+from conv_train_ref import Bottleneck, downsample  # noqa: F401
+from train_common import U, bound  # noqa: F401
 
 # name -> (B, H, W, Cin, Cout, k, seed); stride 2, pad k // 2.  The smallest shapes at which each thing can go wrong.
 CASES = {

@@ -6,6 +6,8 @@ from functools import lru_cache
 import torch
 import torch.nn.functional as Fn
 
+from train_common import U, bound  # noqa: F401 (the unit roundoff and the (L + 2) 2^-24 A bound, under this module's names too)
+
 # name -> (B, H, W, Cin, Cout, k, seed).  The multi-slice cases take their B from ssg_conv_wgrad_num_slices (see multi_slice_batch).
 CASES = {
     "1x1_ragged": (2, 5, 3, 64, 64, 1, 201),        # M = 30: a ragged row tile
@@ -15,8 +17,6 @@ CASES = {
     "3x3_cin192": (2, 4, 4, 192, 64, 3, 205),       # the tile roles swapped for dgrad, six 32-channel chunks
 }
 MULTI = {"multi_1x1": (8, 4, 64, 64, 1, 206), "multi_3x3": (8, 4, 64, 64, 3, 207)}   # (H, W, Cin, Cout, k, seed)
-
-U = 2.0 ** -24
 
 
 def make_case(B, H, W, cin, cout, k, seed):
@@ -44,11 +44,6 @@ def reference(B, H, W, cin, cout, k, seed):
     A = outputs(d["x"].abs(), d["w"].abs(), d["gy"].abs(), d["pad"], torch.float64)
     L = dict(y=k * k * cin, dx=k * k * cout, dw=B * H * W)
     return d, ref, A, L
-
-
-def bound(L, A):
-    """|dev - ref64| <= (L + 2) 2^-24 A: a length-L float32 sum in any order, plus one rounding"""
-    return (L + 2) * U * A
 
 
 def pack_fwd(w):

@@ -14,7 +14,8 @@ import torch
 import torch.nn.functional as Fn
 from torch import nn
 
-from conv_train_ref import U, Bottleneck, bound, downsample  # noqa: F401
+from conv_train_ref import Bottleneck, downsample  # noqa: F401
+from train_common import U, bound  # noqa: F401
 
 # name -> (B, h, w, C, S, seed)
 POOL_CASES = {

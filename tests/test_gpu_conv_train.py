@@ -28,18 +28,14 @@ torch = pytest.importorskip("torch")
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import conv_train_ref as ref  # noqa: E402
+import train_common as tc  # noqa: E402
+from train_common import FLOOR, _lib, _nan  # noqa: E402,F401
 
 pytestmark = pytest.mark.gpu
 
 F_COMP = 4.0
-FLOOR = 2.0 ** -24
 CL = torch.channels_last
 OUTS = ("y", "dx", "dw")
-
-
-def _lib():
-    from ssg_amd import _lib as m
-    return m.lib()
 
 
 def _case(name):
@@ -54,10 +50,6 @@ def _case(name):
 
 
 ALL = tuple(ref.CASES) + tuple(ref.MULTI)
-
-
-def _nan(*shape):
-    return torch.full(shape, float("nan"), dtype=torch.float32, device="cuda")
 
 
 def _api(case, x_cl=True, w_cl=False, x_grad=True, w_grad=True):
@@ -103,14 +95,7 @@ def _abi(case):
 
 
 def _check(case, got, which=OUTS):
-    _, r64, A, L = ref.reference(*case)
-    for o in which:
-        g = got[o].detach().cpu().double()
-        assert g.shape == r64[o].shape and bool(torch.isfinite(g).all()), o
-        err, lim = (g - r64[o]).abs(), ref.bound(L[o], A[o])
-        worst = float((err / lim.clamp_min(1e-300)).max())
-        print("%s %s: max |dev - ref64| = %.3g, worst err / bound = %.3g (L = %d)" % (case[:6], o, float(err.max()), worst, L[o]))
-        assert bool((err <= lim).all()), "%s: %s misses (L + 2) 2^-24 A by a factor of %.3g" % (case[:6], o, worst)
+    tc.check_bound(ref.reference, case, got, which)
 
 
 @pytest.mark.parametrize("name", ALL)
@@ -216,48 +201,23 @@ COMP_SHAPE = (4, 64, 8, 4)
 COMP_MARGIN = 2.0 ** -15
 
 
+def _comp_inputs(g):
+    return torch.randn(*COMP_SHAPE, generator=g), torch.randn(COMP_SHAPE[0], 256, *COMP_SHAPE[2:], generator=g)
+
+
 @lru_cache(maxsize=None)
 def _comp_data():
     """(block in float32 on the CPU, x, gy): the first seed whose ReLU inputs all stay COMP_MARGIN away from 0 in float64"""
-    for seed in range(300, 400):
-        torch.manual_seed(seed)
-        block = ref.Bottleneck(64, 64, 1, ref.downsample(64, 256, 1))
-        for m in block.modules():
-            if isinstance(m, torch.nn.BatchNorm2d):
-                torch.nn.init.uniform_(m.weight, 0.5, 1.5)
-                torch.nn.init.uniform_(m.bias, -0.5, 0.5)
-        g = torch.Generator().manual_seed(seed)
-        x = torch.randn(*COMP_SHAPE, generator=g)
-        gy = torch.randn(COMP_SHAPE[0], 256, *COMP_SHAPE[2:], generator=g)
-        if _comp_margin(block, x) >= COMP_MARGIN:
-            return block, x, gy
-    raise AssertionError("no seed keeps the ReLU inputs away from 0")
+    return tc.quiet_data(range(300, 400), lambda: ref.Bottleneck(64, 64, 1, ref.downsample(64, 256, 1)), _comp_inputs, 3, COMP_MARGIN)
 
 
-def _comp_margin(block, x):
-    b = copy.deepcopy(block).double().train()
-    seen = []
-    h = b.relu.register_forward_pre_hook(lambda mod, inp: seen.append(float(inp[0].detach().abs().min())))
-    b(x.double())
-    h.remove()
-    assert len(seen) == 3
-    return min(seen)
-
-
-def _comp_grads(b, x, gy):
-    b.train()
-    b.zero_grad()
+def _comp_backward(b, x, gy):
     b(x).backward(gy)
-    return {n: p.grad.detach().cpu().double() for n, p in b.named_parameters()}
 
 
 @lru_cache(maxsize=None)
 def _comp_refs():
-    block, x, gy = _comp_data()
-    assert _comp_margin(block, x) >= COMP_MARGIN           # before anything touches the device
-    g64 = _comp_grads(copy.deepcopy(block).double(), x.double(), gy.double())
-    g32 = _comp_grads(copy.deepcopy(block), x, gy)
-    return g64, g32
+    return tc.reference_grads(_comp_data(), 3, COMP_MARGIN, _comp_backward)
 
 
 def _comp_device():
@@ -269,25 +229,17 @@ def _comp_device():
     assert b._ssg_conv_skipped == [] and b._ssg_bn_skipped == []
     assert all(isinstance(getattr(b, n), ssg_amd.Conv2d) for n in ("conv1", "conv2", "conv3")) and isinstance(b.downsample[0], ssg_amd.Conv2d)
     b = b.to(memory_format=CL)
-    return _comp_grads(b, x.cuda().contiguous(memory_format=CL), gy.cuda().contiguous(memory_format=CL))
-
-
-def _err(v, r):
-    return float((v - r).abs().max()) / float(r.abs().max())
+    return tc.grads(b, lambda m: _comp_backward(m, x.cuda().contiguous(memory_format=CL), gy.cuda().contiguous(memory_format=CL)))
 
 
 def measure_composition():
     """[(parameter, err_dev, err_f32)] of the composed block's parameter gradients"""
     g64, g32 = _comp_refs()
-    dev = _comp_device()
-    assert sorted(dev) == sorted(g64)
-    return [(n, _err(dev[n], g64[n]), _err(g32[n], g64[n])) for n in g64]
+    return tc.composition_rows(g64, g32, _comp_device())
 
 
 def test_composition_with_device_batchnorm():
-    for n, e_dev, e_f32 in measure_composition():
-        print("%-22s err_dev %.3g  err_f32 %.3g  ratio %.3g" % (n, e_dev, e_f32, e_dev / e_f32 if e_f32 else float("inf")))
-        assert e_dev <= F_COMP * e_f32 + FLOOR, (n, e_dev, e_f32)
+    tc.check_composition(measure_composition(), F_COMP)
 
 
 def measure():
@@ -295,11 +247,5 @@ def measure():
     rows = []
     for name in ALL:
         case = _case(name)
-        d, r64, A, L = ref.reference(*case)
-        f32 = ref.outputs(d["x"], d["w"], d["gy"], d["pad"], torch.float32)
-        for path, got in (("conv2d_train", _api(case)), ("entry points", _abi(case))):
-            for o in OUTS:
-                err = (got[o].detach().cpu().double() - r64[o]).abs()
-                rows.append((name, case[:6], path, o, float(err.max()), float((f32[o].double() - r64[o]).abs().max()),
-                             float((err / ref.bound(L[o], A[o]).clamp_min(1e-300)).max())))
+        rows += tc.bound_rows(ref.reference, ref.outputs, name, case, (("conv2d_train", _api(case)), ("entry points", _abi(case))), OUTS)
     return rows

@@ -130,7 +130,8 @@ def test_row_minimum_with_several_column_tiles_per_workgroup():
     rng = np.random.default_rng(3)
     x, y = _wide_rows(rng, 4100, 3), _wide_rows(rng, 2500, 3)
     out = torch.empty(4100, dtype=torch.float64, device="cuda")
-    _lib.check(L.ssg_seqdist_rowmin_f64(P(torch.from_numpy(x).cuda()), 4100, P(torch.from_numpy(y).cuda()), 2500, 3, P(out), _lib.stream()), "ssg_seqdist_rowmin_f64")
+    xd, yd = torch.from_numpy(x).cuda(), torch.from_numpy(y).cuda()      # held until the result is read: a temporary's block can be handed out again
+    _lib.check(L.ssg_seqdist_rowmin_f64(P(xd), 4100, P(yd), 2500, 3, P(out), _lib.stream()), "ssg_seqdist_rowmin_f64")
     assert np.array_equal(out.cpu().numpy(), hausdorff_ref.seq_sqdist(x, y).min(axis=1))
 
 

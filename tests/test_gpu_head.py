@@ -30,21 +30,13 @@ torch = pytest.importorskip("torch")
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import head_ref as ref  # noqa: E402
+import train_common as tc  # noqa: E402
+from train_common import FLOOR, _lib, _nan  # noqa: E402,F401
 
 pytestmark = pytest.mark.gpu
 
 F_COMP = 2.0
-FLOOR = 2.0 ** -24
 CL = torch.channels_last
-
-
-def _lib():
-    from ssg_amd import _lib as m
-    return m.lib()
-
-
-def _nan(*shape):
-    return torch.full(shape, float("nan"), dtype=torch.float32, device="cuda")
 
 
 # ---- stripe pooling ------------------------------------------------------------------------------------------------------------------------
@@ -273,54 +265,27 @@ COMP_SHAPE = (8, 3, 16, 8)
 COMP_MARGIN = 2.0 ** -15
 
 
-def _comp_margin(model, x):
-    m = copy.deepcopy(model).double().train()
-    seen = []
-    hooks = [r.register_forward_pre_hook(lambda mod, inp: seen.append(float(inp[0].detach().abs().min())))
-             for r in m.modules() if isinstance(r, torch.nn.ReLU)]
-    m(x.double())
-    for h in hooks:
-        h.remove()
-    assert len(seen) == 5                                        # the stem's, the bottleneck's three and the head's
-    return min(seen)
+def _comp_inputs(g):
+    B = COMP_SHAPE[0]
+    return torch.randn(*COMP_SHAPE, generator=g), [torch.randn(B, 256, generator=g) for _ in range(3)] + [torch.randn(B, 128, generator=g)]
 
 
 @lru_cache(maxsize=None)
 def _comp_data():
     """(model in float32 on the CPU, x, the coefficients of the loss): the first seed whose ReLU inputs all stay COMP_MARGIN away from
-    0 in float64"""
-    for seed in range(700, 800):
-        torch.manual_seed(seed)
-        model = ref.HeadNet(num_split=2, num_classes=0)
-        for m in model.modules():
-            if isinstance(m, torch.nn.modules.batchnorm._BatchNorm):
-                torch.nn.init.uniform_(m.weight, 0.5, 1.5)
-                torch.nn.init.uniform_(m.bias, -0.5, 0.5)
-        g = torch.Generator().manual_seed(seed)
-        x = torch.randn(*COMP_SHAPE, generator=g)
-        B = COMP_SHAPE[0]
-        coef = [torch.randn(B, 256, generator=g) for _ in range(3)] + [torch.randn(B, 128, generator=g)]
-        if _comp_margin(model, x) >= COMP_MARGIN:
-            return model, x, coef
-    raise AssertionError("no seed keeps the ReLU inputs away from 0")
+    0 in float64; the ReLUs run 5 times: the stem's, the bottleneck's three and the head's"""
+    return tc.quiet_data(range(700, 800), lambda: ref.HeadNet(num_split=2, num_classes=0), _comp_inputs, 5, COMP_MARGIN)
 
 
-def _comp_grads(model, x, coef):
-    model.train()
-    model.zero_grad()
+def _comp_backward(model, x, coef):
     outs = ref.flat_outputs(model(x))
     assert [tuple(o.shape) for o in outs] == [tuple(c.shape) for c in coef]
     sum((o * c).sum() for o, c in zip(outs, coef)).backward()          # a fixed linear functional of all outputs
-    return {n: p.grad.detach().cpu().double() for n, p in model.named_parameters() if p.grad is not None}
 
 
 @lru_cache(maxsize=None)
 def _comp_refs():
-    model, x, coef = _comp_data()
-    assert _comp_margin(model, x) >= COMP_MARGIN                 # before anything touches the device
-    g64 = _comp_grads(copy.deepcopy(model).double(), x.double(), [c.double() for c in coef])
-    g32 = _comp_grads(copy.deepcopy(model), x, coef)
-    return g64, g32
+    return tc.reference_grads(_comp_data(), 5, COMP_MARGIN, _comp_backward)
 
 
 def _comp_device():
@@ -337,19 +302,13 @@ def _comp_device():
     m = m.to(memory_format=CL)
     out = m(x.cuda().contiguous(memory_format=CL))
     assert isinstance(out, tuple) and len(out) == 2 and isinstance(out[0], list) and len(out[0]) == 3      # the reference's structure
-    return _comp_grads(m, x.cuda().contiguous(memory_format=CL), [c.cuda() for c in coef])
-
-
-def _err(v, r):
-    return float((v - r).abs().max()) / float(r.abs().max())
+    return tc.grads(m, lambda mod: _comp_backward(mod, x.cuda().contiguous(memory_format=CL), [c.cuda() for c in coef]))
 
 
 def measure_composition():
     """[(parameter, err_dev, err_f32)] of the composed model's parameter gradients"""
     g64, g32 = _comp_refs()
-    dev = _comp_device()
-    assert sorted(dev) == sorted(g64)
-    return [(n, _err(dev[n], g64[n]), _err(g32[n], g64[n])) for n in g64]
+    return tc.composition_rows(g64, g32, _comp_device())
 
 
 def test_composition_is_bit_reproducible():
@@ -361,9 +320,7 @@ def test_composition_is_bit_reproducible():
 
 
 def test_composition_against_float64():
-    for n, e_dev, e_f32 in measure_composition():
-        print("%-32s err_dev %.3g  err_f32 %.3g  ratio %.3g" % (n, e_dev, e_f32, e_dev / e_f32 if e_f32 else float("inf")))
-        assert e_dev <= F_COMP * e_f32 + FLOOR, (n, e_dev, e_f32)
+    tc.check_composition(measure_composition(), F_COMP, 32)
 
 
 def test_device_head_alone_keeps_the_output_structure():

@@ -16,6 +16,7 @@ for p in (ROOT, os.path.join(ROOT, "tests")):
 
 def main():
     import torch
+    from train_common import composition_table
     import conv_strided_ref as ref
     import test_gpu_conv_strided as t
     import test_gpu_maxpool_train as tp
@@ -42,14 +43,7 @@ def main():
     lines.append("composition: Bottleneck(256 -> 512, stride 2) with use_device_conv(strided=True) + use_device_batchnorm, x %r, parameter gradients"
                  % (t.COMP_SHAPE,))
     lines.append("err = max |v - ref64| / max |ref64|; ratio = err_dev / err_f32 (float32 CPU run of the same block)")
-    lines.append("%-24s %11s %11s %9s" % ("parameter", "err_dev", "err_f32", "ratio"))
-    worst_c = 0.0
-    for n, e_dev, e_f32 in t.measure_composition():
-        ratio = e_dev / e_f32 if e_f32 > 0 else float("inf") if e_dev > 0 else 0.0
-        if e_dev > t.FLOOR:
-            worst_c = max(worst_c, ratio)
-        lines.append("%-24s %11.3e %11.3e %9.3g%s" % (n, e_dev, e_f32, ratio, " *" if e_dev > t.FLOOR else ""))
-    lines.append("worst ratio among gradients with err_dev > 2^-24 (*): %.3g; the test asserts F_COMP = %g" % (worst_c, t.F_COMP))
+    lines += composition_table(t.measure_composition(), t.F_COMP, 24)
     with open(out, "w") as f:
         f.write("\n".join(lines) + "\n")
     print("\n".join(lines))

@@ -16,6 +16,7 @@ for p in (ROOT, os.path.join(ROOT, "tests")):
 
 def main():
     import torch
+    from train_common import composition_table
     import test_gpu_head as t
     out = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "head_errors.txt")
     lines = ["train-mode head: stripe pooling and Linear (csrc/head_train.hip) on %s: error against torch's autograd in float64 on the CPU"
@@ -32,14 +33,7 @@ def main():
     lines.append("composition: the look-alike model of tests/head_ref.py (7x7 stem, max-pool, one stride-2 bottleneck, num_split 2, feat, feat_bn) with "
                  "use_device_conv(strided=True) + use_device_maxpool + use_device_batchnorm + use_device_head, images %r, parameter gradients" % (t.COMP_SHAPE,))
     lines.append("err = max |v - ref64| / max |ref64|; ratio = err_dev / err_f32 (float32 CPU run of the unswapped model)")
-    lines.append("%-34s %11s %11s %9s" % ("parameter", "err_dev", "err_f32", "ratio"))
-    worst_c = 0.0
-    for n, e_dev, e_f32 in t.measure_composition():
-        ratio = e_dev / e_f32 if e_f32 > 0 else float("inf") if e_dev > 0 else 0.0
-        if e_dev > t.FLOOR:
-            worst_c = max(worst_c, ratio)
-        lines.append("%-34s %11.3e %11.3e %9.3g%s" % (n, e_dev, e_f32, ratio, " *" if e_dev > t.FLOOR else ""))
-    lines.append("worst ratio among gradients with err_dev > 2^-24 (*): %.3g; the test asserts F_COMP = %g" % (worst_c, t.F_COMP))
+    lines += composition_table(t.measure_composition(), t.F_COMP, 34)
     with open(out, "w") as f:
         f.write("\n".join(lines) + "\n")
     print("\n".join(lines))

@@ -16,12 +16,13 @@ bytes, over the time -- beside the 6290 GB/s a float4 copy reaches on this chip.
 The last lines say whether (b) beats (c) by more than the spread on every line with a ReLU: only then is fuse=True the default of
 use_device_batchnorm."""
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
+
+from _timing import CELL, rounds, verdict  # noqa: E402 (tools/ is the script's own directory)
 
 B = 128
 CALLS, ROUNDS, WARMUP = 5, 7, 3
@@ -88,23 +89,8 @@ def main():
 
             impls = [torch_chain, fused] + ([swap] if relu else [])
 
-            def one(fn):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                torch.autograd.grad(fn(), wrt, gy)
-                e1.record()
-                e1.synchronize()
-                return e0.elapsed_time(e1)
-
-            for fn in impls:
-                for _ in range(WARMUP):
-                    one(fn)
-            meds = [[] for _ in impls]
-            for _ in range(ROUNDS):
-                for i, fn in enumerate(impls):
-                    meds[i].append(statistics.median(one(fn) for _ in range(CALLS)))
-            stats = [(statistics.median(m), min(m), max(m)) for m in meds]
-            cells = ["%9.4f (%.4f-%.4f)" % s for s in stats] + (["-"] if not relu else [])
+            stats = rounds([lambda fn=fn: torch.autograd.grad(fn(), wrt, gy) for fn in impls], CALLS, ROUNDS, WARMUP)
+            cells = [CELL % s for s in stats] + (["-"] if not relu else [])
             gbs = PASSES[variant] * x.numel() * 4 / (stats[1][0] * 1e-3) / 1e9
             c_over_b = "%7.2f" % (stats[2][0] / stats[1][0]) if relu else "      -"
             lines.append("%-22s %-9s %26s %26s %26s %7.2f %s %8.0f" % ("x".join(str(s) for s in shape), variant, cells[0], cells[1], cells[2],
@@ -112,8 +98,7 @@ def main():
             print(lines[-1], flush=True)
             if relu:
                 fused_lines += 1
-                spread = max(stats[1][2] - stats[1][1], stats[2][2] - stats[2][1])
-                fused_wins += int(stats[2][0] - stats[1][0] > spread)
+                fused_wins += int(verdict(stats[1], stats[2], "fused", "swap") == "fused")
         del x, r, gy
         torch.cuda.empty_cache()
     lines.append("fused (b) faster than the plain swap (c) by more than the spread of the round medians on %d of %d lines with a ReLU" % (fused_wins, fused_lines))

@@ -11,12 +11,13 @@ grad) and the weight.  Every call is timed on its own with events; a round takes
 turn, ROUNDS rounds; the table shows the median of the round medians and their min-max (the spread).  A side wins a shape when its
 median is lower by more than the larger of the two spreads, else the line says "tie"."""
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
+
+from _timing import CELL, rounds, verdict  # noqa: E402 (tools/ is the script's own directory)
 
 B = 128
 CALLS, ROUNDS, WARMUP = 5, 7, 3
@@ -49,29 +50,10 @@ def main():
              "%-24s %-22s %26s %26s %6s %-7s %6s" % ("where", "Cin>Cout k HxW", "(a) ms", "(b) ms", "a / b", "winner", "slices")]
     wins = {"torch": 0, "device": 0, "tie": 0}
 
-    def timed(fn):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        return e0.elapsed_time(e1)
-
-    def rounds(fns):
-        for fn in fns:
-            for _ in range(WARMUP):
-                timed(fn)
-        meds = [[] for _ in fns]
-        for _ in range(ROUNDS):
-            for i, fn in enumerate(fns):
-                meds[i].append(statistics.median(timed(fn) for _ in range(CALLS)))
-        return [(statistics.median(m), min(m), max(m)) for m in meds]
-
     def report(where, what, a, b, n):
-        spread = max(a[2] - a[1], b[2] - b[1])
-        winner = "torch" if b[0] - a[0] > spread else "device" if a[0] - b[0] > spread else "tie"
+        winner = verdict(a, b, "torch", "device")
         wins[winner] += 1
-        lines.append("%-24s %-22s %26s %26s %6.2f %-7s %6s" % (where, what, "%9.4f (%.4f-%.4f)" % a, "%9.4f (%.4f-%.4f)" % b, a[0] / b[0], winner, n))
+        lines.append("%-24s %-22s %26s %26s %6.2f %-7s %6s" % (where, what, CELL % a, CELL % b, a[0] / b[0], winner, n))
         print(lines[-1], flush=True)
 
     for cin, cout, k, H, W, where in SHAPES:
@@ -84,7 +66,7 @@ def main():
             OH, OW = ref(x).shape[2:]
         gy = torch.randn((B, cout, OH, OW), device=dev, generator=g).contiguous(memory_format=CL)
         a, b = rounds([lambda: torch.autograd.grad(ref(x), [ref.weight] if stem else [x, ref.weight], gy),
-                       lambda: torch.autograd.grad(mine(x), [mine.weight] if stem else [x, mine.weight], gy)])
+                       lambda: torch.autograd.grad(mine(x), [mine.weight] if stem else [x, mine.weight], gy)], CALLS, ROUNDS, WARMUP)
         report(where, "%d>%d %dx%d %dx%d" % (cin, cout, k, k, H, W), a, b, L.ssg_conv_wgrad_strided_num_slices(B * OH * OW, cout, k, k, cin, 2))
         del x, gy, ref, mine
         torch.cuda.empty_cache()
@@ -92,7 +74,7 @@ def main():
     x = torch.randn((B, C, H, W), device=dev, generator=g).contiguous(memory_format=CL).requires_grad_(True)
     gy = torch.randn((B, C, H // 2, W // 2), device=dev, generator=g).contiguous(memory_format=CL)
     ref, mine = nn.MaxPool2d(3, 2, 1), ssg_amd.MaxPool2d()
-    a, b = rounds([lambda: torch.autograd.grad(ref(x), [x], gy), lambda: torch.autograd.grad(mine(x), [x], gy)])
+    a, b = rounds([lambda: torch.autograd.grad(ref(x), [x], gy), lambda: torch.autograd.grad(mine(x), [x], gy)], CALLS, ROUNDS, WARMUP)
     report(where, "%d 3x3 %dx%d" % (C, H, W), a, b, "-")
     lines.append("of %d shapes: torch faster on %d, the device path faster on %d, within the spread on %d.  The feature is opt-in whatever this says."
                  % (len(SHAPES) + 1, wins["torch"], wins["device"], wins["tie"]))

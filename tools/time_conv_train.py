@@ -12,12 +12,13 @@ the round medians and their min-max (the spread).  A side wins a shape when its 
 spreads, else the line says "tie".  The two stages of the weight gradient (partial tiles on the matrix cores; float64 slice sum) are
 timed the same way through the entry point's `stages` argument, with the number of slices."""
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
+
+from _timing import CELL, rounds, verdict  # noqa: E402 (tools/ is the script's own directory)
 
 B = 128
 CALLS, ROUNDS, WARMUP = 5, 7, 3
@@ -60,24 +61,6 @@ def main():
                                                           "stage 2 ms")]
     wins = {"torch": 0, "device": 0, "tie": 0}
 
-    def timed(fn):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        return e0.elapsed_time(e1)
-
-    def rounds(fns):
-        for fn in fns:
-            for _ in range(WARMUP):
-                timed(fn)
-        meds = [[] for _ in fns]
-        for _ in range(ROUNDS):
-            for i, fn in enumerate(fns):
-                meds[i].append(statistics.median(timed(fn) for _ in range(CALLS)))
-        return [(statistics.median(m), min(m), max(m)) for m in meds]
-
     for cin, cout, k, H, W, where in SHAPES:
         x = torch.randn((B, cin, H, W), device=dev, generator=g).contiguous(memory_format=CL).requires_grad_(True)
         gy = torch.randn((B, cout, H, W), device=dev, generator=g).contiguous(memory_format=CL)
@@ -85,7 +68,8 @@ def main():
         mine = ssg_amd.Conv2d(cin, cout, k, 1, k // 2).to(dev).to(memory_format=CL)
         with torch.no_grad():
             mine.weight.copy_(ref.weight)
-        a, b = rounds([lambda: torch.autograd.grad(ref(x), [x, ref.weight], gy), lambda: torch.autograd.grad(mine(x), [x, mine.weight], gy)])
+        a, b = rounds([lambda: torch.autograd.grad(ref(x), [x, ref.weight], gy), lambda: torch.autograd.grad(mine(x), [x, mine.weight], gy)], CALLS, ROUNDS,
+                      WARMUP)
         M = B * H * W
         n = L.ssg_conv_wgrad_num_slices(M, cout, k, k, cin)
         nws = L.ssg_conv_wgrad_workspace_bytes(M, cout, k, k, cin)
@@ -97,12 +81,11 @@ def main():
         def stage(which):
             return lambda: check(L.ssg_conv_wgrad_f32(ptr(gy), ptr(xd), B, H, W, cin, cout, k, k, ptr(dw), s[0], s[1], s[2], s[3], ptr(ws), nws,
                                                       which, stream()), "ssg_conv_wgrad_f32")
-        s1, s2 = rounds([stage(1), stage(2)])
-        spread = max(a[2] - a[1], b[2] - b[1])
-        winner = "torch" if b[0] - a[0] > spread else "device" if a[0] - b[0] > spread else "tie"
+        s1, s2 = rounds([stage(1), stage(2)], CALLS, ROUNDS, WARMUP)
+        winner = verdict(a, b, "torch", "device")
         wins[winner] += 1
         lines.append("%-30s %-18s %26s %26s %6.2f %-7s %6d %22s %22s" % (
-            where, "%d>%d %dx%d %dx%d" % (cin, cout, k, k, H, W), "%9.4f (%.4f-%.4f)" % a, "%9.4f (%.4f-%.4f)" % b, a[0] / b[0], winner, n,
+            where, "%d>%d %dx%d %dx%d" % (cin, cout, k, k, H, W), CELL % a, CELL % b, a[0] / b[0], winner, n,
             "%8.4f (%.4f-%.4f)" % s1, "%7.4f (%.4f-%.4f)" % s2))
         print(lines[-1], flush=True)
         del x, gy, ws, ref, mine

@@ -11,12 +11,13 @@ call is timed on its own with events; a round takes the median of CALLS calls of
 shows the median of the round medians and their min-max (the spread).  A side wins when its median is lower than (a)'s by more than
 the larger of the two spreads, else the line says "tie"."""
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
+
+from _timing import CELL, rounds, verdict  # noqa: E402 (tools/ is the script's own directory)
 
 B = 128
 CALLS, ROUNDS, WARMUP = 7, 9, 3
@@ -35,30 +36,11 @@ def main():
              "(a) torch's op chain  (b) ssg_amd.stripe_pool_train / linear_train  (c) ssg_amd.conv2d_train on the [B, K, 1, 1] view (feat only)",
              "%-14s %-26s %-4s %28s %7s %-7s" % ("piece", "shape", "impl", "ms", "a / .", "against (a)")]
 
-    def timed(fn):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        return e0.elapsed_time(e1)
-
-    def rounds(fns):
-        for fn in fns:
-            for _ in range(WARMUP):
-                timed(fn)
-        meds = [[] for _ in fns]
-        for _ in range(ROUNDS):
-            for i, fn in enumerate(fns):
-                meds[i].append(statistics.median(timed(fn) for _ in range(CALLS)))
-        return [(statistics.median(m), min(m), max(m)) for m in meds]
-
     def report(piece, shape, res):
         a = res[0]
         for tag, r in zip("abc", res):
-            spread = max(a[2] - a[1], r[2] - r[1])
-            verdict = "-" if r is a else "slower" if r[0] - a[0] > spread else "faster" if a[0] - r[0] > spread else "tie"
-            lines.append("%-14s %-26s %-4s %28s %7.2f %-7s" % (piece, shape, "(%s)" % tag, "%9.4f (%.4f-%.4f)" % r, a[0] / r[0], verdict))
+            word = "-" if r is a else verdict(a, r, "slower", "faster")
+            lines.append("%-14s %-26s %-4s %28s %7.2f %-7s" % (piece, shape, "(%s)" % tag, CELL % r, a[0] / r[0], word))
             print(lines[-1], flush=True)
 
     # the pools
@@ -77,7 +59,7 @@ def main():
         sets = ssg_amd.stripe_pool_train(x, S)
         torch.autograd.grad(list(sets), [x], [gs[0] + gs[S + 1]] + gs[1:S + 1])
 
-    report("pool", "%dx%dx%d S=%d" % (h, w, C, S), rounds([torch_pools, device_pools]))
+    report("pool", "%dx%dx%d S=%d" % (h, w, C, S), rounds([torch_pools, device_pools], CALLS, ROUNDS, WARMUP))
     del x, gs
 
     # the Linears
@@ -93,7 +75,7 @@ def main():
             w4 = wt.detach().view(N, K, 1, 1).requires_grad_(True)
             gy4 = gy.view(B, N, 1, 1).contiguous(memory_format=CL)
             fns.append(lambda: torch.autograd.grad(ssg_amd.conv2d_train(x4, w4), [x4, w4], gy4))
-        report(piece, "B=%d K=%d N=%d%s" % (B, K, N, " +bias" if bias else ""), rounds(fns))
+        report(piece, "B=%d K=%d N=%d%s" % (B, K, N, " +bias" if bias else ""), rounds(fns, CALLS, ROUNDS, WARMUP))
         del xin, wt, bs, gy, fns
     with open(out, "w") as f:
         f.write("\n".join(lines) + "\n")
