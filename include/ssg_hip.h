@@ -721,6 +721,30 @@ int ssg_linear_fwd_f32(const float* x, const float* w, const float* bias, float*
 int ssg_linear_dgrad_f32(const float* dy, const float* w, float* dx, int B, int K, int N, ssg_stream_t stream);
 int ssg_linear_wgrad_f32(const float* dy, const float* x, float* dw, float* db, int B, int K, int N, ssg_stream_t stream);
 
+/* ---- optimiser step of the fine-tune phase: torch.optim.SGD over many tensors (selftraining.py:152-161; csrc/sgd.hip) ---------------
+ * One call updates `count` float32 tensors, each flat: tensor i has numel[i] elements at params[i], grads[i] and bufs[i] (its momentum
+ * buffer; may be NULL when its group's momentum is 0), belongs to group group[i] of num_groups, and first[i] != 0 says that its buffer
+ * holds nothing yet (it is written, not read).  Group k has lr[k], momentum[k], dampening[k], weight_decay[k] (doubles, each rounded to
+ * float32 once; 1 - dampening is formed in double first) and nesterov[k], maximize[k] (ints).  Per element, in float32, torch's
+ * _single_tensor_sgd with every add(., alpha=.) one fused multiply-add, as torch's CPU kernels round:
+ *   g = maximize ? -g : g;   g = weight_decay != 0 ? fma(weight_decay, p, g) : g
+ *   momentum != 0:   buf = first ? g : fma(1 - dampening, g, momentum * buf);   g = nesterov ? fma(momentum, buf, g) : buf
+ *   p = fma(-lr, g, p)
+ * The gradients are not written.  Tensors need 4-byte alignment only; where p, g and buf of a tensor are all 16-byte aligned the
+ * kernel moves float4s, and the bits are the same either way.  The descriptors travel by value in the kernel arguments: a launch
+ * serves up to ssg_sgd_max_tensors_per_launch() descriptors of one group and ssg_sgd_max_chunks_per_launch() chunks (workgroups) of
+ * ssg_sgd_chunk_elems() elements (a power of two); a tensor that does not fit the chunks left in a launch continues in the next.
+ * Nothing is copied to the device, nothing is kept between calls, there is no workspace, no host read and no synchronisation.
+ * count == 0 returns 0 without a launch.  Refused (-1) before any launch: a NULL array with count > 0, num_groups < 1, a NULL
+ * parameter or gradient, a NULL buffer in a group with momentum, numel <= 0, a group index out of range, nesterov with momentum 0 or
+ * dampening != 0, and a negative or non-finite lr, momentum or weight_decay. */
+int ssg_sgd_step_f32(float* const* params, const float* const* grads, float* const* bufs, const int64_t* numel, const int* group, const int* first,
+                     int count, const double* lr, const double* momentum, const double* dampening, const double* weight_decay,
+                     const int* nesterov, const int* maximize, int num_groups, ssg_stream_t stream);
+int ssg_sgd_max_tensors_per_launch(void);
+int ssg_sgd_chunk_elems(void);
+int ssg_sgd_max_chunks_per_launch(void);
+
 #ifdef __cplusplus
 }
 #endif

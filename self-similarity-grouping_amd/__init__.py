@@ -73,6 +73,9 @@ def __getattr__(name):   # lazy: torch import only when the compute surface is t
     if name in ("stripe_pool_train", "linear_train", "Linear", "DeviceHeadMixin", "use_device_head"):
         from . import head
         return getattr(head, name)
+    if name in ("SGD", "use_device_sgd"):
+        from . import sgd
+        return getattr(sgd, name)
     if name in ("DECFinedTrainer2Mixin", "DECJointTrainer2Mixin"):
         from . import trainers
         return getattr(trainers, name)
