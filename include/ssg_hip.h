@@ -745,6 +745,35 @@ int ssg_sgd_max_tensors_per_launch(void);
 int ssg_sgd_chunk_elems(void);
 int ssg_sgd_max_chunks_per_launch(void);
 
+/* ---- embedder refresh: Conv2d + eval-mode BatchNorm folded, packed and split on the device (ssg_amd/resnet.py refresh; csrc/fold.hip) --
+ * One launch writes, for one convolution, exactly the bits the host fold (`_fold` of ssg_amd/resnet.py) produces:
+ *   float64, no contraction, correctly rounded sqrt and division: scale = gamma / sqrt(var + eps), w' = float32(w * scale),
+ *   bias [Cout] = float32(beta - mean * scale).
+ * w is the [Cout,Cin,KH,KW] weight at element strides (s_co, s_ci, s_r, s_s): contiguous or channels_last, no copy; a Linear weight
+ * [N,K] is Cout = N, Cin = K, KH = KW = 1, strides (K, 1, 1, 1).  gamma / beta / mean / var are the BatchNorm's float32 weight, bias,
+ * running_mean and running_var [Cout].  w_out [Cout][Kp] float32 containers, 16-byte aligned:
+ *   Cin % 32 == 0: Kp = KH*KW*Cin, k = ((c/32)*KH*KW + r*KW + s)*32 + c%32;
+ *   Cin == 3 (stem): Kp = 32 * ceil(KH*KW / 8), k = (r*KW + s)*4 + c, zero where c == 3 or k >= 4*KH*KW.
+ * split == 0: w_out holds the packed float32 row; ch_scale is not touched (may be NULL).
+ * split != 0: row scale 2^e, e = clamp(floor(log2(16384 / max|w'_row|)), -40, 40), e = 0 for an all-zero row (taken from the bits of
+ *   the maximum, no log2); v = w' * 2^e, hi = half(v), lo = half(v - float(hi)), stored h8l8 (per 8 values [8 hi][8 lo]; the stem h4l4,
+ *   per 4 values [4 hi][4 lo]); ch_scale [Cout] = 2^-e.
+ * _dual: two 1x1 sources with their own BatchNorm over the same Cout (the [conv3 | downsample] GEMM of a downsample block): each is
+ *   folded and packed on its own, Kp = Cin1 + Cin2 with the first source first, one row scale over the whole row,
+ *   bias = float32(b1) + float32(b2) added in float32.
+ * One workgroup per output row, no atomics, no workspace, no host read.  Refused (-1) before any launch, outputs untouched: Cout % 64
+ * != 0, Cin % 32 != 0 other than the stem's 3 (never in _dual), a packed row longer than ssg_fold_max_k() floats, a _dual source that is
+ * not 1x1, a NULL pointer, a negative stride, w_out not 16-byte aligned.  Non-finite parameters are not refused: they propagate by
+ * IEEE rules into w' and bias, and a row whose maximum is Inf or NaN gets e = -40. */
+int ssg_fold_max_k(void);
+int ssg_fold_conv_bn_f32(const float* w, int64_t s_co, int64_t s_ci, int64_t s_r, int64_t s_s, int Cout, int Cin, int KH, int KW, const float* gamma,
+                         const float* beta, const float* mean, const float* var, double eps, int split, float* w_out, float* bias, float* ch_scale,
+                         ssg_stream_t stream);
+int ssg_fold_conv_bn_dual_f32(const float* w1, int64_t s1_co, int64_t s1_ci, int64_t s1_r, int64_t s1_s, int Cin1, int KH1, int KW1, const float* gamma1,
+                              const float* beta1, const float* mean1, const float* var1, const float* w2, int64_t s2_co, int64_t s2_ci, int64_t s2_r,
+                              int64_t s2_s, int Cin2, int KH2, int KW2, const float* gamma2, const float* beta2, const float* mean2, const float* var2,
+                              double eps, int Cout, int split, float* w_out, float* bias, float* ch_scale, ssg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,6 +18,9 @@ weight as two halves (hi + lo, 22 significand bits) and evaluates the products o
 matrix cores with fp32 accumulation (include/ssg_hip.h, ssg_conv2d_nhwc_x); precision='f32'
 keeps everything on the fp32 matrix cores.  There is no training path through the backbone here (SURVEY.md
 section 2 rows 10-11); the DEC head that trains is `ssg_amd.dce.ClusterAssignment`.
+
+Weights arrive through `load_state_dict()` (host: CPU copies, the float64 fold `_fold` below) or through `refresh(model)` (device: the
+entries stay on the GPU and csrc/fold.hip folds, packs and splits them, bit for bit what `_fold` produces).
 """
 from collections import OrderedDict
 
@@ -188,6 +191,52 @@ def _fold(sd, conv_name, bn_name, stride, pad, device, split=False):
     return f
 
 
+def _fold_mode():
+    """SSG_DEVICE_FOLD: '0' the host fold (`_fold`) everywhere, '1' the device fold (csrc/fold.hip) everywhere; unset: the device fold
+    for a convolution with any tensor on the device, the host fold for one whose tensors are all on the CPU"""
+    return os.environ.get("SSG_DEVICE_FOLD", "")
+
+
+def _bn_keys(conv_name, bn_name):
+    return (conv_name + ".weight", bn_name + ".weight", bn_name + ".bias", bn_name + ".running_mean", bn_name + ".running_var")
+
+
+def _use_device_fold(sd, keys):
+    mode = _fold_mode()
+    return mode == "1" or (mode != "0" and any(sd[k].device.type != "cpu" for k in keys))
+
+
+def _fold_device(sources, stride, pad, device, split=False):
+    """`_fold` on the device, bit for bit (csrc/fold.hip): sources is one (weight, gamma, beta, running_mean, running_var), or two for
+    the [conv3 | downsample] row of a downsample block.  Tensors on another device are moved raw; nothing is read back."""
+    L = _lib.lib()
+    srcs = [[t.detach().to(device, torch.float32) for t in s] for s in sources]
+    w = srcs[0][0]
+    cout, cin, k, kw = w.shape
+    f = _FoldedConv()
+    f.split, f.acc_scale, f.cscale = bool(split), 1.0, None
+    kp = 32 * ((k * kw + 7) // 8) if cin == 3 else sum(s[0].shape[1] * s[0].shape[2] * s[0].shape[3] for s in srcs)
+    f.w = torch.empty((cout, kp), dtype=torch.float32, device=device)
+    f.bias = torch.empty(cout, dtype=torch.float32, device=device)
+    if split:
+        f.cscale = torch.empty(cout, dtype=torch.float32, device=device)
+    if len(srcs) == 1:
+        g, b, m, v = srcs[0][1:]
+        st = w.stride()
+        check(L.ssg_fold_conv_bn_f32(ptr(w), st[0], st[1], st[2], st[3], cout, cin, k, kw, ptr(g), ptr(b), ptr(m), ptr(v), _BN_EPS, 1 if split else 0,
+                                     ptr(f.w), ptr(f.bias), ptr(f.cscale), stream()), "ssg_fold_conv_bn_f32")
+    else:
+        args = []
+        for wt, g, b, m, v in srcs:
+            st = wt.stride()
+            args += [ptr(wt), st[0], st[1], st[2], st[3], wt.shape[1], wt.shape[2], wt.shape[3], ptr(g), ptr(b), ptr(m), ptr(v)]
+        check(L.ssg_fold_conv_bn_dual_f32(*args, _BN_EPS, cout, 1 if split else 0, ptr(f.w), ptr(f.bias), ptr(f.cscale), stream()),
+              "ssg_fold_conv_bn_dual_f32")
+    last = srcs[-1][0]                                # the dual form answers as its downsample convolution (see _prepare)
+    f.cin, f.cout, f.k, f.stride, f.pad = (4 if cin == 3 else last.shape[1]), cout, last.shape[2], stride, pad
+    return f
+
+
 class ResNet:
     """Mirror of reid.models.resnet.ResNet (resnet.py:17-148), forward only."""
 
@@ -223,13 +272,25 @@ class ResNet:
 
     # ---- torch.nn.Module-like surface used by selftraining.py / evaluators.py
     def state_dict(self):
-        return OrderedDict((k, v.clone()) for k, v in self._sd.items())
+        return OrderedDict((k, v.clone() if v.device.type == "cpu" else v.cpu()) for k, v in self._sd.items())
 
     def load_state_dict(self, state_dict, strict=True):
         """torch.nn.Module.load_state_dict look-alike.  Accepts what the reference's call sites pass (selftraining.py:129-132,
         serialization.py:31-40): the checkpoint dict itself ({'state_dict': ...}) and nn.DataParallel's 'module.' key prefix.
         With strict=False torch leaves unmatched keys at their previous (ImageNet) values; here the previous values are
         synthetic, so backbone keys that stay unmatched are reported with a warning instead of silently producing garbage."""
+        state_dict, missing, unexpected = self._match_keys(state_dict, strict)
+        for k, v in state_dict.items():
+            if k in self._sd:
+                if tuple(v.shape) != tuple(self._sd[k].shape):
+                    raise RuntimeError("size mismatch for %s: %r vs %r" % (k, tuple(v.shape), tuple(self._sd[k].shape)))
+                self._sd[k] = v.detach().to("cpu").clone()
+        self._invalidate()
+        self._report_missing("load_state_dict", missing)
+        return missing, unexpected
+
+    def _match_keys(self, state_dict, strict):
+        """-> (the mapping without its {'state_dict': ...} wrapper and 'module.' prefix, missing, unexpected); strict raises"""
         if isinstance(state_dict, dict) and "state_dict" in state_dict and not any(k in self._sd for k in state_dict):
             state_dict = state_dict["state_dict"]
         if state_dict and all(k.startswith("module.") for k in state_dict):
@@ -238,19 +299,40 @@ class ResNet:
         unexpected = [k for k in state_dict if k not in self._sd]
         if strict and (missing or unexpected):
             raise RuntimeError("Error(s) in loading state_dict: missing %r unexpected %r" % (missing[:5], unexpected[:5]))
-        for k, v in state_dict.items():
-            if k in self._sd:
-                if tuple(v.shape) != tuple(self._sd[k].shape):
-                    raise RuntimeError("size mismatch for %s: %r vs %r" % (k, tuple(v.shape), tuple(self._sd[k].shape)))
-                self._sd[k] = v.detach().to("cpu").clone()
-        self._invalidate()
+        return state_dict, missing, unexpected
+
+    def _report_missing(self, who, missing):
         miss_base = [k for k in missing if k.startswith("base.") and not k.endswith("num_batches_tracked")]
         if miss_base:
             import warnings
-            warnings.warn("ssg_amd ResNet.load_state_dict: %d backbone tensors were not in the state dict and keep their synthetic "
-                          "values (first: %s)" % (len(miss_base), miss_base[0]), stacklevel=2)
+            warnings.warn("ssg_amd ResNet.%s: %d backbone tensors were not in the state dict and keep their synthetic "
+                          "values (first: %s)" % (who, len(miss_base), miss_base[0]), stacklevel=3)
         else:
             self._weights = "loaded"
+
+    def refresh(self, source, strict=False):
+        """Take the weights of the model that has just been trained without leaving the device.  source: an nn.Module (nn.DataParallel
+        or any wrapper with `.module` is unwrapped; the train-mode layers of ssg_amd keep the reference's state-dict keys) or a mapping
+        of tensors with load_state_dict's leniency.  Every matched entry becomes a detached clone on this model's device (one
+        stream-ordered copy per tensor: later in-place optimiser steps on the source do not reach the embedder), and the folded
+        weights are rebuilt at once by csrc/fold.hip -- no host copy, no host read, no synchronisation.  Shapes are checked before
+        anything changes.  state_dict() afterwards still returns CPU tensors; load_state_dict() puts what it is given back on the CPU."""
+        if self.device.type != "cuda":
+            raise _lib.SSGError("refresh() keeps the weights on the GPU: call model.cuda() first (load_state_dict() is the host route)")
+        while not hasattr(source, "keys") and getattr(source, "module", None) is not None and source.module is not source:
+            source = source.module
+        if not hasattr(source, "keys"):
+            source = source.state_dict()
+        state_dict, missing, unexpected = self._match_keys(source, strict)
+        for k, v in state_dict.items():
+            if k in self._sd and tuple(v.shape) != tuple(self._sd[k].shape):
+                raise RuntimeError("size mismatch for %s: %r vs %r" % (k, tuple(v.shape), tuple(self._sd[k].shape)))
+        for k, v in state_dict.items():
+            if k in self._sd:
+                self._sd[k] = v.detach().to(self.device, copy=True)
+        self._invalidate()
+        self._report_missing("refresh", missing)
+        self._prepare()
         return missing, unexpected
 
     def eval(self):
@@ -285,41 +367,63 @@ class ResNet:
         return self
 
     # ---- weights
+    def _host_sd(self, keys):
+        """the entries `_fold` reads, on the CPU (device entries are copied back: SSG_DEVICE_FOLD=0)"""
+        return {k: self._sd[k].cpu() for k in keys}
+
+    def _fold_one(self, conv_name, bn_name, stride, pad, split=False):
+        """one convolution + BatchNorm: the device fold when any of its tensors is on the device, else the host fold (`_fold_mode`)"""
+        keys = _bn_keys(conv_name, bn_name)
+        if _use_device_fold(self._sd, keys):
+            return _fold_device([[self._sd[k] for k in keys]], stride, pad, self.device, split=split)
+        return _fold(self._host_sd(keys), conv_name, bn_name, stride, pad, self.device, split=split)
+
+    def _fold_dual(self, p, stride, sp):
+        """-> (c3, ds) of a downsample bottleneck: the downsample branch fused into conv3, one GEMM over K = planes + inplanes (the
+        residual tensor is never written to / re-read from HBM); both halves share one weight scale.  ds.w = [conv3 | downsample]
+        along K, ds.bias = b3 + b_ds; c3 is conv3 folded on its own (the forward takes its cin / cout)."""
+        dev = self.device
+        k3, kd = _bn_keys(p + ".conv3", p + ".bn3"), _bn_keys(p + ".downsample.0", p + ".downsample.1")
+        if _use_device_fold(self._sd, k3 + kd):
+            c3 = _fold_device([[self._sd[k] for k in k3]], 1, 0, dev)
+            ds = _fold_device([[self._sd[k] for k in k3], [self._sd[k] for k in kd]], stride, 0, dev, split=sp)
+            return c3, ds
+        sd = self._host_sd(k3 + kd)
+        c3 = _fold(sd, p + ".conv3", p + ".bn3", 1, 0, dev)
+        ds = _fold(sd, p + ".downsample.0", p + ".downsample.1", stride, 0, dev)
+        wcat = torch.cat([c3.w, ds.w], dim=1)
+        if sp:
+            sc = _row_scales(wcat.cpu())
+            ds.w = _h8l8((wcat.cpu() * sc.view(-1, 1))).to(dev); ds.acc_scale = 1.0; ds.cscale = (1.0 / sc).contiguous().to(dev); ds.split = True
+        else:
+            ds.w = wcat.contiguous()
+        ds.bias = (c3.bias + ds.bias).contiguous()
+        return c3, ds
+
     def _prepare(self):
         if self._folded is not None:
             return self._folded
         if self.device.type != "cuda":
             raise _lib.SSGError("the embedder runs on the GPU only: call model.cuda() first (no CPU fallback)")
-        sd, dev = self._sd, self.device
         sp = self.precision == "split"
-        net = dict(stem=_fold(sd, "base.conv1", "base.bn1", 2, 3, dev, split=sp), blocks=[], split=sp)
+        fold = self._fold_one
+        net = dict(stem=fold("base.conv1", "base.bn1", 2, 3, sp), blocks=[], split=sp)
         for blk in _arch(self.depth):
             p = blk["prefix"]
             if blk["kind"] == "basic":
                 net["blocks"].append(dict(
                     kind="basic",
-                    c1=_fold(sd, p + ".conv1", p + ".bn1", blk["stride"], 1, dev, split=sp),
-                    c2=_fold(sd, p + ".conv2", p + ".bn2", 1, 1, dev, split=sp),
-                    ds=_fold(sd, p + ".downsample.0", p + ".downsample.1", blk["stride"], 0, dev, split=sp) if blk["down"] else None))
+                    c1=fold(p + ".conv1", p + ".bn1", blk["stride"], 1, sp),
+                    c2=fold(p + ".conv2", p + ".bn2", 1, 1, sp),
+                    ds=fold(p + ".downsample.0", p + ".downsample.1", blk["stride"], 0, sp) if blk["down"] else None))
                 continue
             if blk["down"]:
-                # downsample branch fused into conv3: one GEMM over K = planes + inplanes (the residual tensor
-                # is never written to / re-read from HBM); both halves share one weight scale
-                c3 = _fold(sd, p + ".conv3", p + ".bn3", 1, 0, dev)
-                ds = _fold(sd, p + ".downsample.0", p + ".downsample.1", blk["stride"], 0, dev)
-                wcat = torch.cat([c3.w, ds.w], dim=1)
-                if sp:
-                    sc = _row_scales(wcat.cpu())
-                    ds.w = _h8l8((wcat.cpu() * sc.view(-1, 1))).to(dev); ds.acc_scale = 1.0; ds.cscale = (1.0 / sc).contiguous().to(dev); ds.split = True
-                else:
-                    ds.w = wcat.contiguous()
-                ds.bias = (c3.bias + ds.bias).contiguous()
+                c3, ds = self._fold_dual(p, blk["stride"], sp)
             else:
-                c3 = _fold(sd, p + ".conv3", p + ".bn3", 1, 0, dev, split=sp)
-                ds = None
+                c3, ds = fold(p + ".conv3", p + ".bn3", 1, 0, sp), None
             net["blocks"].append(dict(
-                c1=_fold(sd, p + ".conv1", p + ".bn1", 1, 0, dev, split=sp),
-                c2=_fold(sd, p + ".conv2", p + ".bn2", blk["stride"], 1, dev, split=sp),
+                c1=fold(p + ".conv1", p + ".bn1", 1, 0, sp),
+                c2=fold(p + ".conv2", p + ".bn2", blk["stride"], 1, sp),
                 c3=c3, ds=ds))
         self._folded = net
         return net
@@ -532,10 +636,16 @@ class ResNet:
             return None
         net = self._prepare()
         if "feat" not in net:
-            sd = dict(self._sd)
-            sd["feat.weight4"] = sd["feat.weight"].view(self.num_features, self.out_planes, 1, 1)
-            f = _fold({"c.weight": sd["feat.weight4"], "b.weight": sd["feat_bn.weight"], "b.bias": sd["feat_bn.bias"],
-                       "b.running_mean": sd["feat_bn.running_mean"], "b.running_var": sd["feat_bn.running_var"]}, "c", "b", 1, 0, self.device)
+            keys = _bn_keys("feat", "feat_bn")
+            if _use_device_fold(self._sd, keys):
+                src = [self._sd[k] for k in keys]
+                src[0] = src[0].unsqueeze(-1).unsqueeze(-1)                       # [N, K] as a 1x1 convolution, whatever its strides
+                f = _fold_device([src], 1, 0, self.device)
+            else:
+                sd = self._host_sd(keys)
+                f = _fold({"c.weight": sd["feat.weight"].view(self.num_features, self.out_planes, 1, 1), "b.weight": sd["feat_bn.weight"],
+                           "b.bias": sd["feat_bn.bias"], "b.running_mean": sd["feat_bn.running_mean"], "b.running_var": sd["feat_bn.running_var"]},
+                          "c", "b", 1, 0, self.device)
             net["feat"] = f
         B = gap.shape[0]
         out = self._conv(_lib.lib(), gap.reshape(B, 1, 1, self.out_planes).contiguous(), net["feat"], relu=True)
