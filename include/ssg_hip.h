@@ -745,6 +745,54 @@ int ssg_sgd_max_tensors_per_launch(void);
 int ssg_sgd_chunk_elems(void);
 int ssg_sgd_max_chunks_per_launch(void);
 
+/* ---- classification losses of the fine-tune phase: softmax cross-entropy with a per-row factor, accuracy, the OIM table
+ * (reid/loss/triplet.py:79-106 FocalLoss, reid/loss/weight_cross_entropy.py, reid/loss/oim.py, nn.CrossEntropyLoss of reid/eug.py:132,
+ * reid/evaluation_metrics/classification.py; csrc/softmax_ce.hip) -----------------------------------------------------------------------
+ * x [B,C] float32 logits with a row stride ldx >= C in elements; base and rows need 4-byte alignment only -- a row that is 16-byte
+ * aligned moves as float4s, and the bits are the same either way.  target [B] int64.  B >= 1 and C >= 1, B up to the grid limit.
+ * Forward, per row i with t = target[i], everything in float64:
+ *   lse_i   = max_j x[i][j] + log(sum_j exp(x[i][j] - max))      a thread adds the quads q = tid, tid + 256, ... of the row in ascending
+ *                                                                column order; the 256 partial sums by a fixed tree
+ *   logpt_i = x[i][t] - lse_i
+ *   s_i     = row_w[i] * class_w[t] * (1 - exp(logpt_i))^gamma   an absent weight (NULL) counts as 1; gamma == 0 gives the factor 1
+ *   loss_i  = -s_i * logpt_i                                     row_loss [B] float32 (may be NULL)
+ * A row is staged in LDS up to ssg_softmax_ce_row_capacity() floats; a longer row is read from memory a second time instead (the same
+ * order, the same bits).  lse [B] and s [B] float64 are kept for the backward.  reduction: 0 none (loss is not written, r = 1),
+ * 1 sum (r = 1), 2 mean over B (r = 1 / B), 3 weighted mean (r = 1 / W, W = sum of row_w[i] * class_w[t] over the rows that are not
+ * ignored: torch's rule for `weight=` with reduction='mean').  The batch loss is the float64 sum of the row losses in ascending row order,
+ * divided and rounded once to the float32 *loss, by a second launch of one workgroup that also writes *r (float64, kept on the device
+ * for the backward).  A row with t == ignore_index has s = 0 and loss 0 and is in no denominator; all rows ignored gives NaN under 3.
+ * A target outside [0, C) that is not ignore_index never indexes memory: s_i = NaN, so loss_i, the batch loss and that row of dx are
+ * NaN, and it counts in W with class weight 1, so that every other row keeps its finite gradient.
+ * Backward: dx[i][j] = (g[i * g_stride] * r * s_i) * (exp(x[i][j] - lse_i) - [j == t]) in float64, rounded once; g is read on the
+ * device with g_stride 0 (a scalar upstream gradient) or 1 (one per row, reduction none).  Every element of dx [B,C] (row stride
+ * lddx >= C) is written exactly once; an ignored row gets zeros.  The factor s is a constant of the backward (the reference detaches pt).
+ * 1 launch, B * ceil(C / 1024) workgroups (at most 2^31 - 1).
+ * No float atomics, no workspace, no host read.  Refused (-1) before any launch: B < 1, C < 1, a row stride below C, a reduction code
+ * outside 0..3, a negative or non-finite gamma, g_stride outside {0, 1}, a NULL pointer other than row_w, class_w, row_loss (and loss
+ * under reduction 0). */
+int ssg_softmax_ce_row_capacity(void);
+int ssg_softmax_ce_fwd_f32(const float* x, int64_t ldx, const int64_t* target, int64_t ignore_index, const float* row_w, const float* class_w,
+                           double gamma, int reduction, int B, int C, double* lse, double* s, double* r, float* row_loss, float* loss,
+                           ssg_stream_t stream);
+int ssg_softmax_ce_bwd_f32(const float* x, int64_t ldx, const int64_t* target, int64_t ignore_index, const double* lse, const double* s,
+                           const double* r, const float* g, int g_stride, float* dx, int64_t lddx, int B, int C, ssg_stream_t stream);
+/* accuracy: rank[i] = #{j : x[i][j] > x[i][t] or (x[i][j] == x[i][t] and j < t)} -- a tie goes to the lower index; C for a target outside
+ * [0, C), which is never correct and never an index -- then out[a] = float(#{i : rank[i] < ks[a]}) * (float)(1.0 / B), the float32
+ * product of torch's correct_k.mul_(1. / batch_size).  ks is a host array of num_k values >= 1, 1 <= num_k <= ssg_topk_correct_max_k();
+ * rank [B] int32 and out [num_k] float32 on the device.  Integer counts: 2 launches, no atomics on floats, no host read. */
+int ssg_topk_correct_max_k(void);
+int ssg_topk_correct_f32(const float* x, int64_t ldx, const int64_t* target, int B, int C, const int* ks, int num_k, int* rank, float* out,
+                         ssg_stream_t stream);
+/* OIM table update (oim.py:24-26): for the rows b of the batch in order, y = target[b]: v = momentum * lut[y] + (1 - momentum) * x[b],
+ * lut[y] = v / |v|.  Each step reads the float32 table row, forms v, the norm (a fixed order) and the quotient in float64 and rounds
+ * once to float32; a zero norm gives NaN as in the reference.  Rows with the same target are applied in batch order by the workgroup of
+ * the first of them; a target outside [0, C) updates nothing.  x [B,F] with row stride ldx >= F, lut [C,F] with row stride ldl >= F.
+ * 1 launch, no workspace.  Refused (-1) before any launch: B, C or F < 1, a row stride below F, a negative or non-finite momentum, a
+ * NULL pointer. */
+int ssg_oim_update_f32(const float* x, int64_t ldx, const int64_t* target, float* lut, int64_t ldl, int B, int C, int F, double momentum,
+                       ssg_stream_t stream);
+
 /* ---- embedder refresh: Conv2d + eval-mode BatchNorm folded, packed and split on the device (ssg_amd/resnet.py refresh; csrc/fold.hip) --
  * One launch writes, for one convolution, exactly the bits the host fold (`_fold` of ssg_amd/resnet.py) produces:
  *   float64, no contraction, correctly rounded sqrt and division: scale = gamma / sqrt(var + eps), w' = float32(w * scale),

@@ -76,6 +76,9 @@ def __getattr__(name):   # lazy: torch import only when the compute surface is t
     if name in ("SGD", "use_device_sgd"):
         from . import sgd
         return getattr(sgd, name)
+    if name in ("CrossEntropyLoss", "FocalLoss", "WeightCE", "OIMLoss", "oim", "accuracy", "cross_entropy_train"):
+        from . import loss
+        return getattr(loss, name)
     if name in ("DECFinedTrainer2Mixin", "DECJointTrainer2Mixin"):
         from . import trainers
         return getattr(trainers, name)
