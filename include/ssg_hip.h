@@ -822,6 +822,47 @@ int ssg_fold_conv_bn_dual_f32(const float* w1, int64_t s1_co, int64_t s1_ci, int
                               int64_t s2_s, int Cin2, int KH2, int KW2, const float* gamma2, const float* beta2, const float* mean2, const float* var2,
                               double eps, int Cout, int split, float* w_out, float* bias, float* ch_scale, ssg_stream_t stream);
 
+/* ---- affinity propagation on a precomputed similarity matrix (ssg_amd.cluster.AffinityPropagation; csrc/affinity.hip) ----------------
+ * sklearn 1.7.2's _affinity_propagation in float64 with numpy's bits: every damped update rounds twice (no contraction), the column
+ * sums add the rows in ascending order with one running sum per column, argmax takes the first maximum.  S, A, R, noise are row-major
+ * [N,N] float64 (indexed with size_t); N >= 1.  No float atomics, and no host read in any of these calls.
+ * ssg_ap_median_f64: out[0] = np.median of the n values of X: the middle order statistic, or (a + b) / 2 of the two middle ones when
+ *   n is even -- an exact radix select over order-preserving 64-bit keys (13-bit digits, 10 launches); ws of
+ *   ssg_ap_median_workspace_bytes() bytes, 8-byte aligned.  X must hold no NaN.
+ * ssg_ap_stats_f64: the device form of the input check and of _equal_similarities_and_preferences, on the matrix as the caller gave it.
+ *   pref [pref_n] float64 on the device, pref_n = 1 or N.  stats [8] int64: [0] non-finite entries of S (diagonal included),
+ *   [1] / [2] minimum / maximum of the finite off-diagonal entries as order-preserving keys (key = ~bits for a negative value, else
+ *   bits | 2^63; ~0 / 0 when there is none), [3] / [4] the same of pref, [5] non-finite entries of pref, [6] the bits of S[0][N-1],
+ *   [7] the bits of pref[0].
+ * ssg_ap_prepare_f64: S.flat[::N+1] = pref, then S += (eps64 * S + tiny64 * 100) * noise with the three roundings in that order.
+ * One iteration `it` (0-based) is: ssg_ap_row_f64(it, do_r = 1), ssg_ap_colsum_f64, the convergence check -- ssg_ap_iterate_f64 queues
+ * `count` of them from it0 on.  A, R [N,N], cs [N] float64, window [N][convergence_iter] and E [N] uint8 and ctrl [8] int64 start as
+ * zeros.  ctrl[0] = 1 once sklearn's stopping rule fired, ctrl[1] = its n_iter (it + 1), ctrl[2] = K of the last check.
+ *   row: the A update of iteration it - 1 (A = A*d - (1-d)*T, T = clip(max(R,0) - cs, 0, inf) off the diagonal, R - cs on it; skipped
+ *     for it = 0) and then, when do_r, the R update of iteration it (R = R*d + (1-d)*(S - Y), Y2 at the first argmax of A + S).  One
+ *     workgroup per row, 16-byte accesses when N is even.
+ *   colsum: cs[k] = sum over i ascending of max(R[i][k], 0), the diagonal taken from R itself.
+ *   check: E[k] = (A'[k][k] + R[k][k] > 0) with A' the value the next row call stores, the window column it % convergence_iter, the rule.
+ *   Once ctrl[0] is set, the row call with it == ctrl[1] applies that A update and nothing else; every other call leaves A, R, cs,
+ *   window and E untouched.  After the last iteration `last` the caller queues ssg_ap_row_f64(it = last + 1, do_r = 0) in every case.
+ * ssg_ap_finish_f64: I [N] int32 = flatnonzero(E) (K = ctrl[2] entries, the rest untouched), c = argmax_k S[:, I] with c[I] = arange(K),
+ *   sums[j] = the sum of S[i][j] over the members i of j's cluster in ascending i, I[k] = the member with the largest sum (lowest index on
+ *   ties), c again.  labels = I[c] is left to the host.  K = 0 writes nothing but ctrl[2]. */
+size_t ssg_ap_median_workspace_bytes(void);
+int ssg_ap_median_f64(const double* X, int64_t n, void* ws, size_t ws_bytes, double* out, ssg_stream_t stream);
+int ssg_ap_stats_f64(const double* S, int N, const double* pref, int pref_n, int64_t* stats, ssg_stream_t stream);
+int ssg_ap_prepare_f64(double* S, int N, const double* pref, int pref_n, const double* noise, ssg_stream_t stream);
+int ssg_ap_row_f64(const double* S, double* A, double* R, const double* cs, int N, double damping, int it, int do_r, const int64_t* ctrl,
+                   ssg_stream_t stream);
+int ssg_ap_colsum_f64(const double* R, int N, double* cs, const int64_t* ctrl, ssg_stream_t stream);
+/* the same with tile `cfg` of the column walk, 0 <= cfg < ssg_ap_colsum_configs() (-1: chosen by the number of workgroups, as above);
+ * every tile gives the same bits -- for tools/time_affinity.py --sweep and the tests */
+int ssg_ap_colsum_configs(void);
+int ssg_ap_colsum_cfg_f64(const double* R, int N, double* cs, const int64_t* ctrl, int cfg, ssg_stream_t stream);
+int ssg_ap_iterate_f64(const double* S, double* A, double* R, double* cs, uint8_t* window, uint8_t* E, int64_t* ctrl, int N, double damping,
+                       int convergence_iter, int it0, int count, ssg_stream_t stream);
+int ssg_ap_finish_f64(const double* S, const uint8_t* E, int N, int32_t* I, int32_t* c, double* sums, int64_t* ctrl, ssg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

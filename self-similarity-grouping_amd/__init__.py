@@ -8,7 +8,7 @@ this package is the thin host-side mirror of the reference interface.
 from . import _lib  # noqa: F401
 from ._lib import SSGError, available  # noqa: F401
 
-__all__ = ["re_ranking", "re_ranking_device", "DBSCAN", "eps_rule", "eps_rule_dbscan", "compute_dist", "generate_selflabel", "SSGError", "available"]
+__all__ = ["re_ranking", "re_ranking_device", "DBSCAN", "AffinityPropagation", "eps_rule", "eps_rule_dbscan", "compute_dist", "generate_selflabel", "SSGError", "available"]
 
 
 def __getattr__(name):   # lazy: torch import only when the compute surface is touched
@@ -21,10 +21,10 @@ def __getattr__(name):   # lazy: torch import only when the compute surface is t
     if name == "generate_selflabel_semi":
         from . import semitraining
         return semitraining.generate_selflabel
-    if name in ("DBSCAN", "eps_rule", "eps_rule_dbscan", "as_handle"):
+    if name in ("DBSCAN", "AffinityPropagation", "eps_rule", "eps_rule_dbscan", "as_handle"):
         from . import cluster
         return getattr(cluster, name)
-    if name in ("compute_dist", "generate_selflabel", "select_labeled", "generate_dataset"):
+    if name in ("compute_dist", "generate_selflabel", "generate_selflabel_affinity", "select_labeled", "generate_dataset"):
         from . import selftraining
         return getattr(selftraining, name)
     if name in ("extract_features", "extract_embeddings", "extract_cnn_feature", "fliplr", "pairwise_distance", "pairwise_distance_device",

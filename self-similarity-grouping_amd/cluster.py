@@ -6,6 +6,9 @@ arguments, `fit`, `fit_predict`, `labels_`, `core_sample_indices_`, same label n
 (clusters numbered by their smallest core index; border points take the smallest cluster id
 among their core neighbours; noise = -1).  It accepts a numpy/torch matrix, or the
 `DistHandle` / `DeviceBackedArray` produced by `ssg_amd.rerank` (no re-upload).
+
+`AffinityPropagation` (at the end of the file) is the same kind of look-alike for the clustering the reference imports beside DBSCAN
+(selftraining.py:27, switch-over lines :302-308), for affinity='precomputed' on one GPU.
 """
 import math
 import numbers
@@ -635,3 +638,249 @@ class DBSCAN:
 
     def fit_predict(self, X, y=None, sample_weight=None):
         return self.fit(X, sample_weight=sample_weight).labels_
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# affinity propagation (the clustering selftraining.py:27 imports beside DBSCAN; its switch-over lines are :302-308)
+
+try:
+    from sklearn.exceptions import ConvergenceWarning
+except Exception:                                       # sklearn is optional: the same name, the same place in the hierarchy
+    class ConvergenceWarning(UserWarning):
+        """Custom warning to capture convergence problems"""
+
+
+_AP_NOISE = {}          # (N, seed, device index) -> device noise matrix of an int seed (sklearn reseeds on every fit: the same matrix each time)
+
+
+def _check_random_state(seed):
+    """sklearn.utils.check_random_state"""
+    if seed is None or seed is np.random:
+        return np.random.mtrand._rand
+    if isinstance(seed, numbers.Integral):
+        return np.random.RandomState(seed)
+    if isinstance(seed, np.random.RandomState):
+        return seed
+    raise ValueError("%r cannot be used to seed a numpy.random.RandomState instance" % seed)
+
+
+def _read_back(*tensors):
+    """THE blocking host read of the affinity propagation path: every tensor travels as one DMA copy into pooled page-locked memory
+    behind the queued kernels, then one wait.  -> numpy arrays (the tests count the calls of this function)."""
+    from . import hostio
+    outs = []
+    for t in tensors:
+        o = hostio.pinned_empty(t.shape, t.dtype)
+        o.copy_(t, non_blocking=True)
+        outs.append(o)
+    torch.cuda.current_stream(tensors[0].device).synchronize()
+    return [o.numpy().copy() for o in outs]
+
+
+def _unkey(k):
+    """order-preserving 64-bit key of ssg_ap_stats_f64 -> float"""
+    k = int(k) & 0xFFFFFFFFFFFFFFFF
+    u = (k & 0x7FFFFFFFFFFFFFFF) if k >> 63 else (~k & 0xFFFFFFFFFFFFFFFF)
+    return float(np.uint64(u).view(np.float64))
+
+
+class AffinityPropagation:
+    """sklearn.cluster.AffinityPropagation (1.7.2) look-alike for affinity='precomputed' running on the GPU: the same constructor,
+    `fit`, `fit_predict`, `cluster_centers_indices_`, `labels_`, `n_iter_`, the same warnings -- and, for float64 input and an int
+    `random_state`, the same exemplars, labels and iteration count bit for bit (the loop's float64 arithmetic is numpy's, in numpy's
+    summation order; csrc/affinity.hip).
+
+    Differences from sklearn:
+      * float16 and float32 similarities are widened to float64 first (sklearn keeps float32 arithmetic for float32 input);
+      * `affinity_matrix_` is a CUDA tensor (S with preference and noise applied) and stays on the GPU;
+      * `affinity='euclidean'` and `predict` are not implemented; one GPU only (no sharded input, no active process group);
+      * a `DistHandle` is a distance, not a similarity, and is refused: pass `-h.final_dist()`.
+    The noise `RandomState(seed).standard_normal((N, N))` is drawn by numpy on the host (its streams are frozen, so an int seed gives
+    sklearn's matrix) and uploaded once; with an int seed the device copy is kept for the next fit at the same N.  Memory: S, A, R and
+    the noise, 4 x 8 N^2 bytes.
+
+    Keywords beyond sklearn's: `poll_every` (the stopping flag is read from the device once per that many iterations; launches past
+    convergence change nothing) on the constructor; `stages=` on fit (a dict: 'after' = iteration counts -> the run fills 'S',
+    'A' / 'R' {count: tensor} and 'A_final' / 'R_final'; each count re-runs the loop from zero: debugging and tests only)."""
+
+    def __init__(self, *, damping=0.5, max_iter=200, convergence_iter=15, copy=True, preference=None, affinity="euclidean", verbose=False,
+                 random_state=None, poll_every=16):
+        self.damping, self.max_iter, self.convergence_iter, self.copy = damping, max_iter, convergence_iter, copy
+        self.preference, self.affinity, self.verbose, self.random_state, self.poll_every = preference, affinity, verbose, random_state, poll_every
+
+    def _validate(self):
+        def real(x):
+            return isinstance(x, numbers.Real) and not isinstance(x, bool)
+        if not real(self.damping) or not (0.5 <= float(self.damping) < 1.0):
+            raise ValueError("The 'damping' parameter of AffinityPropagation must be a float in the range [0.5, 1.0). Got %r instead." % (self.damping,))
+        for name in ("max_iter", "convergence_iter"):
+            v = getattr(self, name)
+            if not isinstance(v, numbers.Integral) or isinstance(v, bool) or v < 1:
+                raise ValueError("The '%s' parameter of AffinityPropagation must be an int in the range [1, inf). Got %r instead." % (name, v))
+        if not isinstance(self.copy, (bool, np.bool_)):
+            raise ValueError("The 'copy' parameter of AffinityPropagation must be an instance of 'bool' or an instance of 'numpy.bool_'. "
+                             "Got %r instead." % (self.copy,))
+        if not isinstance(self.poll_every, numbers.Integral) or self.poll_every < 1:
+            raise ValueError("The 'poll_every' parameter of AffinityPropagation must be an int in the range [1, inf). Got %r instead." % (self.poll_every,))
+        if self.affinity != "precomputed":
+            raise ValueError("ssg_amd.cluster.AffinityPropagation implements affinity='precomputed' only (the SSG grouping path, "
+                             "selftraining.py:302-308); got affinity=%r" % (self.affinity,))
+        _check_random_state(self.random_state)
+
+    def _similarity(self, X):
+        """-> contiguous float64 [N,N] CUDA tensor (the caller's own when copy=False allows it)"""
+        if isinstance(X, DistHandle) or callable(getattr(X, "valid_handle", None)) and isinstance(X.valid_handle(), DistHandle):
+            h = X if isinstance(X, DistHandle) else X.valid_handle()
+            if h.group is not None:
+                raise ValueError("AffinityPropagation runs on a single GPU: a row-sharded DistHandle is not supported")
+            raise TypeError("AffinityPropagation takes a SIMILARITY matrix; a DistHandle holds distances: pass -h.final_dist()")
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            raise ValueError("AffinityPropagation runs on a single GPU: call it outside an active process group (world size %d)" % dist.get_world_size())
+        if isinstance(X, np.ndarray):
+            if X.dtype.kind not in "fiu":
+                raise ValueError("AffinityPropagation: a numeric similarity matrix is required, got dtype %s" % X.dtype)
+            t, own = torch.from_numpy(np.ascontiguousarray(X, dtype=np.float64)), False
+        elif torch.is_tensor(X):
+            t, own = X, X.is_cuda
+        else:
+            raise TypeError("unsupported similarity matrix type %r" % type(X))
+        if t.dim() != 2:
+            raise ValueError("Expected 2D array, got %dD array instead" % t.dim())
+        if t.shape[0] != t.shape[1]:
+            raise ValueError("The matrix of similarities must be a square array. Got %r instead." % (tuple(t.shape),))
+        if t.shape[0] < 1:
+            raise ValueError("Found array with 0 sample(s) (shape=%r) while a minimum of 1 is required by AffinityPropagation." % (tuple(t.shape),))
+        if own:
+            dev = t.device
+            if t.dtype == torch.float64 and t.is_contiguous():
+                return t.clone() if self.copy else t
+            return t.to(torch.float64).contiguous()
+        dev = torch.device("cuda", torch.cuda.current_device())
+        return t.to(device=dev, dtype=torch.float64).contiguous()       # host data: the upload is the copy
+
+    def _noise(self, N, dev):
+        seed = self.random_state
+        key = (N, int(seed), dev.index) if isinstance(seed, numbers.Integral) else None
+        if key is not None and key in _AP_NOISE:
+            return _AP_NOISE[key]
+        from . import hostio
+        host = hostio.pinned_empty((N, N), torch.float64)
+        host.numpy()[...] = _check_random_state(seed).standard_normal(size=(N, N))
+        noise = host.to(dev, non_blocking=True)
+        torch.cuda.current_stream(dev).synchronize()      # (the page-locked block goes back to the pool: the copy must have left it)
+        if key is not None:
+            for k in [k for k in _AP_NOISE if k[2] == dev.index]:
+                del _AP_NOISE[k]                           # one matrix per device: 8 N^2 bytes each
+            _AP_NOISE[key] = noise
+        return noise
+
+    def fit(self, X, y=None, *, stages=None):
+        self._validate()
+        import warnings
+        L = _lib.lib()
+        S = self._similarity(X)
+        N, dev = int(S.shape[0]), S.device
+        with torch.cuda.device(dev):
+            return self._fit(L, S, N, dev, stages, warnings)
+
+    def _fit(self, L, S, N, dev, stages, warnings):
+        st = stream()
+        d, ci, max_iter = float(self.damping), int(self.convergence_iter), int(self.max_iter)
+        self.affinity_matrix_, self.n_features_in_ = S, N
+        # ---- preference: np.median of the matrix as given (an exact select on the device), a scalar or a vector
+        if self.preference is None:
+            pref = torch.empty(1, dtype=torch.float64, device=dev)
+            ws_bytes = int(L.ssg_ap_median_workspace_bytes())
+            ws = torch.empty(ws_bytes // 8, dtype=torch.int64, device=dev)
+            check(L.ssg_ap_median_f64(ptr(S), N * N, ptr(ws), ws_bytes, ptr(pref), st), "ssg_ap_median_f64")
+        else:
+            p = np.asarray(self.preference, dtype=np.float64).reshape(-1)
+            if p.size not in (1, N):
+                raise ValueError("AffinityPropagation: preference must be a scalar or an array of n_samples = %d values, got %d" % (N, p.size))
+            pref = torch.from_numpy(np.ascontiguousarray(p)).to(dev)
+        pref_n = int(pref.numel())
+        stats_t = torch.empty(8, dtype=torch.int64, device=dev)
+        check(L.ssg_ap_stats_f64(ptr(S), N, ptr(pref), pref_n, ptr(stats_t), st), "ssg_ap_stats_f64")
+        stats, = _read_back(stats_t)                                                          # read 1: the input check
+        if int(stats[0]):
+            raise ValueError("Input contains NaN or infinity.")
+        if int(stats[5]):
+            raise ValueError("AffinityPropagation: preference contains NaN or infinity.")
+        s_last = float(stats[6:7].view(np.float64)[0])
+        p_first = float(stats[7:8].view(np.float64)[0])
+        equal = N == 1 or (_unkey(stats[3]) == _unkey(stats[4]) and _unkey(stats[1]) == _unkey(stats[2]))
+        if stages is not None:
+            stages["preference"] = pref.clone()
+        if equal:
+            # sklearn's early return: one cluster, or every sample its own, chosen by the preference; S is left as it came
+            warnings.warn("All samples have mutually equal similarities. Returning arbitrary cluster center(s).")
+            if p_first > s_last:
+                self.cluster_centers_indices_, self.labels_ = np.arange(N), np.arange(N)
+            else:
+                self.cluster_centers_indices_, self.labels_ = np.array([0]), np.array([0] * N)
+            self.n_iter_ = 0
+            return self
+        noise = self._noise(N, dev)
+        check(L.ssg_ap_prepare_f64(ptr(S), N, ptr(pref), pref_n, ptr(noise), st), "ssg_ap_prepare_f64")
+        if stages is not None:
+            stages["S"] = S.clone()
+
+        def state():
+            z = torch.zeros((2, N, N), dtype=torch.float64, device=dev)
+            return dict(A=z[0], R=z[1], cs=torch.zeros(N, dtype=torch.float64, device=dev), win=torch.zeros((N, ci), dtype=torch.uint8, device=dev),
+                        E=torch.zeros(N, dtype=torch.uint8, device=dev), ctrl=torch.zeros(8, dtype=torch.int64, device=dev))
+
+        def iterate(s, it0, count):
+            check(L.ssg_ap_iterate_f64(ptr(S), ptr(s["A"]), ptr(s["R"]), ptr(s["cs"]), ptr(s["win"]), ptr(s["E"]), ptr(s["ctrl"]), N, d, ci, it0, count, st),
+                  "ssg_ap_iterate_f64")
+
+        def tail(s, it):
+            check(L.ssg_ap_row_f64(ptr(S), ptr(s["A"]), ptr(s["R"]), ptr(s["cs"]), N, d, it, 0, ptr(s["ctrl"]), st), "ssg_ap_row_f64")
+
+        if stages is not None:
+            stages["A"], stages["R"] = {}, {}
+            for cnt in sorted(set(int(c) for c in stages.get("after", ()))):
+                s = state()
+                cnt = max(1, min(cnt, max_iter))
+                iterate(s, 0, cnt)
+                tail(s, cnt)
+                stages["A"][cnt], stages["R"][cnt] = s["A"].clone(), s["R"].clone()
+                del s
+        s = state()
+        it, done, n_iter = 0, False, max_iter
+        poll = int(self.poll_every)
+        while it < max_iter:
+            cnt = min(poll, max_iter - it)
+            iterate(s, it, cnt)
+            it += cnt
+            ctrl, = _read_back(s["ctrl"])                                                     # one read per poll_every iterations
+            if int(ctrl[0]):
+                done, n_iter = True, int(ctrl[1])
+                break
+        tail(s, it)                    # the last iteration's A update (a no-op when the row call behind the firing check has done it)
+        if self.verbose:
+            print("Converged after %d iterations." % (n_iter - 1) if done else "Did not converge")
+        fin = torch.zeros(2 * N, dtype=torch.int32, device=dev)
+        sums = torch.empty(N, dtype=torch.float64, device=dev)
+        check(L.ssg_ap_finish_f64(ptr(S), ptr(s["E"]), N, ptr(fin[:N]), ptr(fin[N:]), ptr(sums), ptr(s["ctrl"]), st), "ssg_ap_finish_f64")
+        fin_h, ctrl = _read_back(fin, s["ctrl"])                                              # the read at the end
+        if stages is not None:
+            stages["A_final"], stages["R_final"] = s["A"], s["R"]
+        K = int(ctrl[2])
+        self.n_iter_ = n_iter
+        if K > 0:
+            if not done:
+                warnings.warn("Affinity propagation did not converge, this model may return degenerate cluster centers and labels.", ConvergenceWarning)
+            I, c = fin_h[:K].astype(np.int64), fin_h[N:].astype(np.int64)
+            labels = I[c]
+            self.cluster_centers_indices_ = np.unique(labels)
+            self.labels_ = np.searchsorted(self.cluster_centers_indices_, labels)
+        else:
+            warnings.warn("Affinity propagation did not converge and this model will not have any cluster centers.", ConvergenceWarning)
+            self.labels_ = np.array([-1] * N)
+            self.cluster_centers_indices_ = []
+        return self
+
+    def fit_predict(self, X, y=None, *, stages=None):
+        return self.fit(X, stages=stages).labels_

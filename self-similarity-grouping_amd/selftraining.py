@@ -12,7 +12,7 @@ return structure so that selftraining.py can import them instead of its own defi
 import numpy as np
 import torch
 
-from .cluster import DBSCAN, as_handle, eps_rule, eps_rule_dbscan  # noqa: F401
+from .cluster import DBSCAN, AffinityPropagation, as_handle, eps_rule, eps_rule_dbscan  # noqa: F401
 from .rerank import DeviceBackedArray, re_ranking_device
 
 
@@ -98,6 +98,41 @@ def generate_selflabel(e_dist, r_dist, n_iter, args, cluster_list=[]):   # noqa:
             print('Clustering and labeling...')
             labels = cluster.fit_predict(tmp_dist)
         num_ids = len(set(labels.tolist())) - 1
+        print('Iteration {} have {} training ids'.format(n_iter + 1, num_ids))
+        labels_list.append(labels)
+    return labels_list, cluster_list
+
+
+def _similarity(dist):
+    """-1.0 * the distance as a float64 CUDA tensor the estimator may overwrite; a device handle is negated on the device"""
+    from .rerank import DistHandle
+    valid = getattr(dist, "valid_handle", None)
+    h = dist if isinstance(dist, DistHandle) else (valid() if callable(valid) else None)
+    if isinstance(h, DistHandle):
+        if h.group is not None:
+            raise ValueError("generate_selflabel_affinity runs on a single GPU: a row-sharded DistHandle is not supported")
+        f = h.final_dist()
+        return torch.neg(f) if h.mode == 2 else f.neg_()       # (mode 2: final_dist() is the handle's own matrix)
+    return torch.neg(torch.as_tensor(np.asarray(dist) if not torch.is_tensor(dist) else dist).to(_dev(), torch.float64))
+
+
+def generate_selflabel_affinity(e_dist, r_dist, n_iter, args, cluster_list=[]):   # noqa: B006 (mutable default kept: reference :280)
+    """selftraining.py:280-313 with its commented lines switched on (:302 `rerank_dist = -1.0 * rerank_dist  #for similarity matrix`,
+    :308 `num_ids = len(set(labels))  ##for affinity_propagation cluster`): affinity propagation on the negated distance instead of the
+    eps rule + DBSCAN.  The estimator is created at iteration 0 and cached in `cluster_list`; `args` needs `.no_rerank` and may carry
+    `.ap_damping` (0.5), `.ap_preference` (None: the median) and `.ap_seed` (0)."""
+    labels_list = []
+    for s in range(len(r_dist)):
+        tmp_dist = e_dist[s] if args.no_rerank else r_dist[s]
+        if n_iter == 0:
+            cluster = AffinityPropagation(affinity='precomputed', copy=False, damping=getattr(args, "ap_damping", 0.5),
+                                          preference=getattr(args, "ap_preference", None), random_state=getattr(args, "ap_seed", 0))
+            cluster_list.append(cluster)
+        else:
+            cluster = cluster_list[s]
+        print('Clustering and labeling...')
+        labels = cluster.fit_predict(_similarity(tmp_dist))
+        num_ids = len(set(labels.tolist()))
         print('Iteration {} have {} training ids'.format(n_iter + 1, num_ids))
         labels_list.append(labels)
     return labels_list, cluster_list
