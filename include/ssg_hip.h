@@ -304,6 +304,23 @@ int ssg_conv2d_nhwc_x(const void* in, const void* w, const float* bias, const vo
 int ssg_conv1x1_dual_nhwc_x(const void* in, const void* in2, const void* w, const float* bias, void* out, int B, int H, int W, int Cin,
                             int H2, int W2, int Cin2, int stride2, int Cout, int relu, int flags, float acc_scale, const float* ch_scale,
                             int32_t* overflow, ssg_stream_t stream);
+/* Tiled weights.  The LDS-DMA kernel behind the two entry points above streams its weight stages 16 rows x 64 bytes at a time; from the
+ * row-major w that is half a cache line per row.  ssg_conv_weights_tile writes the same containers k-tile-major:
+ * wt [Cout/128][Kpad/16][128 rows][64 B], slot pc (16 bytes) of row r holding the row's chunk pc ^ ((r >> 2) & 3) of that k-tile, so that
+ * every DMA instruction reads 1 KB contiguous.  Returns 1 when wt was written, 0 when the shape has no tiled form (Cout % 128 or
+ * Kpad % 16, see ssg_conv_weights_tile_supported; nothing is written), negative on error.  wt: Cout * Kpad containers, not overlapping w.
+ * The _xt entry points are the _x ones plus that pointer (NULL = row-major everywhere); only the three-product LDS-DMA launches read it,
+ * w stays required, and the result is bit-identical either way.  flags & SSG_CONV_W_TILED hands the same copy to the _x entry points
+ * without the pointer: it then lies right behind w (wt == (float*)w + Cout * Kpad). */
+#define SSG_CONV_W_TILED 4
+int ssg_conv_weights_tile_supported(int Cout, int Kpad);
+int ssg_conv_weights_tile(const void* w, int Cout, int Kpad, void* wt, ssg_stream_t stream);
+int ssg_conv2d_nhwc_xt(const void* in, const void* w, const void* wt, const float* bias, const void* res, void* out, int B, int H, int W, int Cin,
+                       int Cout, int KH, int KW, int stride, int pad, int relu, int flags, float acc_scale, const float* ch_scale,
+                       int32_t* overflow, ssg_stream_t stream);
+int ssg_conv1x1_dual_nhwc_xt(const void* in, const void* in2, const void* w, const void* wt, const float* bias, void* out, int B, int H, int W, int Cin,
+                             int H2, int W2, int Cin2, int stride2, int Cout, int relu, int flags, float acc_scale, const float* ch_scale,
+                             int32_t* overflow, ssg_stream_t stream);
 /* Round 6, experimental (opt-in through SSG_CONV_PAIR=1 in the Python layer): the tail of one identity bottleneck block and the head of the
  * next as ONE launch -- out [M,C] = relu(conv3_1x1(y2 [M,K1]) + b3 + res [M,C]) (base.py:84-90) and y1n [M,N2] = relu(conv1_1x1(out) + b1n)
  * (base.py:76-78 of the next block); every tensor h8l8, weights as ssg_conv2d_nhwc_x takes them (w3 [C][K1], w1n [N2][C], rows

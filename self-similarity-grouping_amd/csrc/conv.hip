@@ -84,6 +84,8 @@ struct ConvParams {
   // 1 = only the hi x hi product of the split-half operands (a plain fp16 GEMM: 1/3 of the matrix work, error 2^-10 |x||y|;
   // used by the source-term bound pass, whose tolerance covers it); 3 = the fp32-class three-product form
   int products = 3;
+  // conv_dma_kernel, three-product instances: the same weights in the k-tile-major layout ssg_conv_weights_tile writes (nullptr = read `w`)
+  const float* wt = nullptr;
   unsigned long long* prof = nullptr;   // SSG_DMA_PROF builds (tools/micro/conv_prof.hip): 8 s_memtime stamps per workgroup of conv_dma_kernel
 };
 #ifdef SSG_DMA_PROF
@@ -606,12 +608,23 @@ __global__ __launch_bounds__((BM / WM_) * (BN / 64) * 64, BM == 256 ? 1 : (BN ==
 #undef SSG_ROW
   const __amdgpu_buffer_rsrc_t in_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.in), 0, p.in_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t in2_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.in2 ? p.in2 : p.in), 0, p.in2 ? p.in2_bytes : 0u, 0x00020000);
-  const __amdgpu_buffer_rsrc_t w_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.w), 0, (unsigned)((int64_t)p.Cout * p.Kpad * 4), 0x00020000);
-  const unsigned wo0 = (unsigned)(((tn * BN + wave * (16 * WBLK) + drow) * p.Kpad + lc4) * 4), wo1 = wo0 + (unsigned)(16 * p.Kpad * 4);
+  // Weight stages.  Row-major `w` [Cout][Kpad]: a DMA instruction fetches 16 rows x one 64-byte piece at a pitch of Kpad * 4 bytes (half a
+  // cache line per row).  Tiled `wt` (ssg_conv_weights_tile): [Cout / 128][Kpad / 16] granules of 128 rows x 64 bytes with the slot swizzle
+  // already applied, i.e. the byte image of this stage part -- lane l reads base + 16 * l, 1 KB contiguous per instruction.  The choice is
+  // wave-uniform and made here, once: the loop below adds the same two offsets either way (kb_ = dn << wkshift instead of dn << 6).
+#ifndef SSG_CONV_WT
+#define SSG_CONV_WT 1          /* 0: ignore ConvParams.wt (A/B builds: tools/ab_inproc.py interleaves the two libraries) */
+#endif
+  const int nk = p.Kpad / CBK;
+  const bool tiled = SSG_CONV_WT && !ONEPROD && p.wt != nullptr;
+  const __amdgpu_buffer_rsrc_t w_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(tiled ? p.wt : p.w), 0, (unsigned)((int64_t)p.Cout * p.Kpad * 4), 0x00020000);
+  const int wrow0 = tn * BN + wave * (16 * WBLK);                  // first weight row of this wave's block(s): both lie in one 128-row granule
+  const unsigned wo0 = tiled ? (unsigned)((((wrow0 >> 7) * nk) * 128 + (wrow0 & 127)) * 64 + lane * 16) : (unsigned)(((wrow0 + drow) * p.Kpad + lc4) * 4);
+  const unsigned wo1 = wo0 + (tiled ? 1024u : (unsigned)(16 * p.Kpad * 4));
+  const int wkshift = tiled ? 13 : 6;                              // log2 of the bytes from one k-tile to the next: an 8 KB granule, or CBK * 4
   // DMA cursor: the next k-tile to fetch is dn = ((chunk dch) * KH*KW + tap (dr, ds)) * 2 + half; it only ever moves forward by one
   // (clamped at the last tile), so the tap decode is a few scalar increments instead of two integer divisions per tile and wave,
   // and a lane's address is its tap-(0,0) offset + one uniform delta (out-of-range taps: the offset is replaced, not clamped).
-  const int nk = p.Kpad / CBK;
   int dn = 0, dr = 0, ds = 0, dch = 0;
 #ifndef SSG_DMA_AUX_A
 #define SSG_DMA_AUX_A 0        /* cache policy of the activation DMA (2 = nt): A/B knob, measured neutral */
@@ -634,7 +647,7 @@ __global__ __launch_bounds__((BM / WM_) * (BN / 64) * 64, BM == 256 ? 1 : (BN ==
   {                                                                                                                  \
     const int ddelta_ = ((dr * p.W + ds) * p.Cin + dch * 32 + (dn & 1) * 16) * 4;                                     \
     SSG_DMA_A(0, ST) if (ABLK == 2) SSG_DMA_A(1, ST)                                                                  \
-    const unsigned kb_ = (unsigned)(dn * CBK * 4);                                                                    \
+    const unsigned kb_ = (unsigned)dn << wkshift;                                                                     \
     __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rsrc, SSG_LDSP(ST + BM * 64 + wave * (1024 * WBLK)), 16, wo0 + kb_, 0, 0, SSG_DMA_AUX_W);   \
     if (WBLK == 2) __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rsrc, SSG_LDSP(ST + BM * 64 + wave * 2048 + 1024), 16, wo1 + kb_, 0, 0, SSG_DMA_AUX_W); \
     {                                        /* branch-free advance; the tail re-fetches the last tile (harmless, keeps the vmcnt accounting uniform) */ \
@@ -1034,6 +1047,19 @@ __global__ __launch_bounds__((BM / WM_) * (BN / 64) * 64, BM == 256 ? 1 : (BN ==
   }
 }
 
+// Tiled copy of a folded weight for conv_dma_kernel's weight stages: w [Cout][Kpad] containers -> wt [Cout / 128][Kpad / 16] granules of
+// [128 rows][4 slots of 16 bytes]; slot pc of row r holds the row's logical 16-byte chunk pc ^ ((r >> 2) & 3) of that k-tile (the stage
+// swizzle, applied here once).  One thread per slot; run once per fold, so the 64-byte pieces it reads at the row pitch do not matter.
+__global__ __launch_bounds__(256) void conv_weights_tile_kernel(const uint4* __restrict__ w, uint4* __restrict__ wt, int nk, int64_t nslots) {
+  const int64_t s = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (s >= nslots) return;
+  const int64_t gran = s >> 9;                                      // 512 slots per granule
+  const int row = (int)(s >> 2) & 127, pc = (int)s & 3;
+  const int64_t gc = gran / nk; const int kt = (int)(gran - gc * nk);
+  const int lc = pc ^ ((row >> 2) & 3);
+  wt[s] = w[((gc * 128 + row) * nk + kt) * 4 + lc];                 // a row is nk k-tiles of 4 chunks
+}
+
 // NCHW float32 images [B,3,H,W] -> NHWC4 [B,H,W,4] (4th channel 0), optional horizontal flip
 // (reid/evaluators.py:12-16 fliplr fused into the layout change).
 __global__ void nchw_to_nhwc4_kernel(const float* __restrict__ in, float* __restrict__ out, int B, int H, int W, int flip) {
@@ -1294,9 +1320,35 @@ static bool conv_prefers_bn64(const ConvParams& p, bool split) {
 // flags: SSG_CONV_IN_SPLIT (1) = in and w are in the split-half h8l8 format (w additionally pre-multiplied by
 // 1/acc_scale, a power of two), the GEMM runs on the fp16 matrix cores (3 products per term, fp32 accumulate);
 // SSG_CONV_OUT_SPLIT (2) = out (and res) are written / read in h8l8.  flags = 0 is the plain fp32 path.
-extern "C" int ssg_conv2d_nhwc_x(const void* in, const void* w, const float* bias, const void* res, void* out, int B, int H, int W,
-                                 int Cin, int Cout, int KH, int KW, int stride, int pad, int relu, int flags, float acc_scale, const float* ch_scale,
-                                 int32_t* overflow, hipStream_t stream) {
+//
+// wt (nullable): the tiled copy of w that ssg_conv_weights_tile wrote; the three-product LDS-DMA launches read their weight stages from it,
+// every other kernel reads w.  SSG_CONV_W_TILED (4) in flags says the same without the pointer: the copy lies right behind w's Cout * Kpad
+// containers.  The result does not depend on it.
+extern "C" int ssg_conv_weights_tile_supported(int Cout, int Kpad) { return Cout > 0 && Kpad > 0 && Cout % 128 == 0 && Kpad % 16 == 0; }
+
+// -> 1: wt holds the tiled copy of w (Cout * Kpad containers, same size as w; must not overlap it); 0: this shape has none, nothing is written
+extern "C" int ssg_conv_weights_tile(const void* w, int Cout, int Kpad, void* wt, hipStream_t stream) {
+  if (!ssg_conv_weights_tile_supported(Cout, Kpad)) return 0;
+  if (!w || !wt || (((uintptr_t)w | (uintptr_t)wt) & 15)) { ssg_set_error("ssg_conv_weights_tile: w and wt must be given and 16-byte aligned"); return SSG_ERR_INVALID; }
+  const int64_t nslots = (int64_t)Cout * Kpad / 4;
+  hipLaunchKernelGGL(conv_weights_tile_kernel, dim3((unsigned)((nslots + 255) / 256)), dim3(256), 0, stream, (const uint4*)w, (uint4*)wt, Kpad / 16, nslots);
+  SSG_LAUNCH_CHECK("conv_weights_tile_kernel");
+  return 1;
+}
+
+static const void* conv_tiled_weights(const char* fn, const void* w, const void* wt, int flags, int Cout, int64_t Kpad, int* rc) {
+  *rc = SSG_OK;
+  if (!wt && (flags & 4)) wt = (const float*)w + (int64_t)Cout * Kpad;
+  if (wt && (!(flags & 1) || !ssg_conv_weights_tile_supported(Cout, (int)Kpad))) {
+    ssg_set_error("%s: tiled weights need split-half operands, Cout %% 128 == 0 and Kpad %% 16 == 0 (Cout=%d Kpad=%lld flags=%d)", fn, Cout, (long long)Kpad, flags);
+    *rc = SSG_ERR_INVALID;
+  }
+  return wt;
+}
+
+extern "C" int ssg_conv2d_nhwc_xt(const void* in, const void* w, const void* wt, const float* bias, const void* res, void* out, int B, int H, int W,
+                                  int Cin, int Cout, int KH, int KW, int stride, int pad, int relu, int flags, float acc_scale, const float* ch_scale,
+                                  int32_t* overflow, hipStream_t stream) {
   ConvParams p;
   p.cscale = ch_scale; p.overflow = overflow;
   p.in = (const float*)in; p.w = (const float*)w; p.bias = bias; p.res = (const float*)res; p.out = (float*)out;
@@ -1320,9 +1372,16 @@ extern "C" int ssg_conv2d_nhwc_x(const void* in, const void* w, const float* bia
   const bool cin4 = (Cin == 4);
   p.Kpad = cin4 ? 32 * ((KH * KW + 7) / 8) : KH * KW * Cin;
   p.nk1 = p.Kpad / 16;   // no second input: every k-tile (of either BK) reads `in`
+  { int rc; p.wt = (const float*)conv_tiled_weights("ssg_conv2d_nhwc_xt", w, wt, flags, Cout, p.Kpad, &rc); if (rc) return rc; }
   if (cin4) return (Cout % 128 == 0) ? launch_conv<128, 128, 64, 64, true>(p, stream, split) : launch_conv<128, 64, 64, 32, true>(p, stream, split);
   if (conv_prefers_wide(p, split)) return launch_conv_wide(p, stream);
   return (Cout % 128 == 0 && !conv_prefers_bn64(p, split)) ? launch_conv<128, 128, 64, 64, false>(p, stream, split) : launch_conv<128, 64, 64, 32, false>(p, stream, split);
+}
+
+extern "C" int ssg_conv2d_nhwc_x(const void* in, const void* w, const float* bias, const void* res, void* out, int B, int H, int W,
+                                 int Cin, int Cout, int KH, int KW, int stride, int pad, int relu, int flags, float acc_scale, const float* ch_scale,
+                                 int32_t* overflow, hipStream_t stream) {
+  return ssg_conv2d_nhwc_xt(in, w, nullptr, bias, res, out, B, H, W, Cin, Cout, KH, KW, stride, pad, relu, flags, acc_scale, ch_scale, overflow, stream);
 }
 
 extern "C" int ssg_conv2d_nhwc_f32(const float* in, const float* w, const float* bias, const float* res, float* out, int B, int H, int W,
@@ -1334,9 +1393,9 @@ extern "C" int ssg_conv2d_nhwc_f32(const float* in, const float* w, const float*
 // self.downsample is not None):  out = relu( conv3(in) + bn3 + downsample_conv(in2) + bn_ds )
 // as ONE implicit GEMM over the concatenated K = Cin + Cin2: w [Cout][Cin + Cin2], bias = b3 + b_ds.
 // in [B,H,W,Cin] (1x1, stride 1); in2 [B,H2,W2,Cin2] sampled at (oh*stride2, ow*stride2).
-extern "C" int ssg_conv1x1_dual_nhwc_x(const void* in, const void* in2, const void* w, const float* bias, void* out, int B, int H, int W,
-                                       int Cin, int H2, int W2, int Cin2, int stride2, int Cout, int relu, int flags, float acc_scale, const float* ch_scale,
-                                       int32_t* overflow, hipStream_t stream) {
+extern "C" int ssg_conv1x1_dual_nhwc_xt(const void* in, const void* in2, const void* w, const void* wt, const float* bias, void* out, int B, int H, int W,
+                                        int Cin, int H2, int W2, int Cin2, int stride2, int Cout, int relu, int flags, float acc_scale, const float* ch_scale,
+                                        int32_t* overflow, hipStream_t stream) {
   ConvParams p;
   p.cscale = ch_scale; p.overflow = overflow;
   p.in = (const float*)in; p.w = (const float*)w; p.bias = bias; p.res = nullptr; p.out = (float*)out;
@@ -1354,8 +1413,15 @@ extern "C" int ssg_conv1x1_dual_nhwc_x(const void* in, const void* in2, const vo
   p.Kpad = Cin + Cin2; p.nk1 = Cin / 32; p.variant = 0; p.rowterm = nullptr; p.epi = 0; p.tilemin = nullptr; p.tmin_ld = 0;   // dual input stays on BK=32 (nk1 counts 32-wide tiles)
   p.out_split = (flags & 2) ? 1 : 0; p.res_split = p.out_split; p.acc_scale = acc_scale;
   const bool split = (flags & 1) != 0;
+  { int rc; p.wt = (const float*)conv_tiled_weights("ssg_conv1x1_dual_nhwc_xt", w, wt, flags, Cout, p.Kpad, &rc); if (rc) return rc; }
   if (conv_prefers_wide(p, split)) return launch_conv_wide(p, stream);
   return (Cout % 128 == 0 && !conv_prefers_bn64(p, split)) ? launch_conv<128, 128, 64, 64, false>(p, stream, split) : launch_conv<128, 64, 64, 32, false>(p, stream, split);
+}
+
+extern "C" int ssg_conv1x1_dual_nhwc_x(const void* in, const void* in2, const void* w, const float* bias, void* out, int B, int H, int W,
+                                       int Cin, int H2, int W2, int Cin2, int stride2, int Cout, int relu, int flags, float acc_scale, const float* ch_scale,
+                                       int32_t* overflow, hipStream_t stream) {
+  return ssg_conv1x1_dual_nhwc_xt(in, in2, w, nullptr, bias, out, B, H, W, Cin, H2, W2, Cin2, stride2, Cout, relu, flags, acc_scale, ch_scale, overflow, stream);
 }
 
 extern "C" int ssg_conv1x1_dual_nhwc_f32(const float* in, const float* in2, const float* w, const float* bias, float* out, int B, int H, int W,

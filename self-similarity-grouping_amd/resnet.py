@@ -112,10 +112,30 @@ def synthetic_state_dict(seed=1, depth=50, num_features=2048, randomize_bn=True,
 
 
 class _FoldedConv:
-    __slots__ = ("w", "bias", "cin", "cout", "k", "stride", "pad", "split", "acc_scale", "cscale")
+    __slots__ = ("w", "bias", "cin", "cout", "k", "stride", "pad", "split", "acc_scale", "cscale", "wt")
 
 
-_IN_SPLIT, _OUT_SPLIT = 1, 2      # include/ssg_hip.h SSG_CONV_IN_SPLIT / SSG_CONV_OUT_SPLIT
+_IN_SPLIT, _OUT_SPLIT, _W_TILED = 1, 2, 4      # include/ssg_hip.h SSG_CONV_IN_SPLIT / SSG_CONV_OUT_SPLIT / SSG_CONV_W_TILED
+
+
+def _attach_tiled(f):
+    """f.wt: the k-tile-major copy of a split-half weight (ssg_conv_weights_tile) the LDS-DMA convolution launches stream their weight
+    stages from, or None where there is no tiled form (stem, Cout % 128).  f.w moves into the first half of one buffer and the copy
+    takes the second, so that the flag SSG_CONV_W_TILED is all a launch needs; made on the device, once per fold."""
+    f.wt = None
+    cout, kp = f.w.shape
+    if not f.split or f.cin == 4 or f.w.device.type != "cuda":
+        return f
+    L = _lib.lib()
+    if not L.ssg_conv_weights_tile_supported(cout, kp):
+        return f
+    both = torch.empty((2, cout, kp), dtype=torch.float32, device=f.w.device)
+    both[0].copy_(f.w)
+    rc = L.ssg_conv_weights_tile(ptr(both[0]), cout, kp, ptr(both[1]), stream())
+    if rc != 1:
+        check(rc if rc < 0 else -2, "ssg_conv_weights_tile")
+    f.w, f.wt = both[0], both[1]
+    return f
 
 
 def _h8l8(v):
@@ -188,7 +208,7 @@ def _fold(sd, conv_name, bn_name, stride, pad, device, split=False):
         f.cscale = (1.0 / sc).contiguous().to(device)
     f.w = w.to(device); f.bias = bias.float().contiguous().to(device)
     f.cin, f.cout, f.k, f.stride, f.pad = cin, cout, k, stride, pad
-    return f
+    return _attach_tiled(f)
 
 
 def _fold_mode():
@@ -234,7 +254,7 @@ def _fold_device(sources, stride, pad, device, split=False):
               "ssg_fold_conv_bn_dual_f32")
     last = srcs[-1][0]                                # the dual form answers as its downsample convolution (see _prepare)
     f.cin, f.cout, f.k, f.stride, f.pad = (4 if cin == 3 else last.shape[1]), cout, last.shape[2], stride, pad
-    return f
+    return _attach_tiled(f)
 
 
 class ResNet:
@@ -259,6 +279,9 @@ class ResNet:
         self._sd = synthetic_state_dict(seed, depth, num_features, cluster=bool(cluster))
         self._folded = None
         self._twin = None
+        # the LDS-DMA convolution launches read their weight stages from the tiled copies (`_attach_tiled`); read at every forward, so both
+        # layouts can be compared in one process.  SSG_CONV_WT=0 sets the default only.  Same bits either way.
+        self.tiled_weights = os.environ.get("SSG_CONV_WT", "1") != "0"
         self.flip_streams = True         # embed_with_flip: the original and the flipped forward on two HIP streams (SSG_FLIP_STREAMS=0: one)
         self._weights = "synthetic"      # until load_state_dict puts real backbone weights in
         if checkpoint:
@@ -395,6 +418,7 @@ class ResNet:
         if sp:
             sc = _row_scales(wcat.cpu())
             ds.w = _h8l8((wcat.cpu() * sc.view(-1, 1))).to(dev); ds.acc_scale = 1.0; ds.cscale = (1.0 / sc).contiguous().to(dev); ds.split = True
+            _attach_tiled(ds)
         else:
             ds.w = wcat.contiguous()
         ds.bias = (c3.bias + ds.bias).contiguous()
@@ -430,22 +454,22 @@ class ResNet:
 
     # ---- forward
     @staticmethod
-    def _conv(L, x, f, res=None, relu=True, out_split=False, ovf=None):
+    def _conv(L, x, f, res=None, relu=True, out_split=False, ovf=None, tiled=False):
         B, H, W, _ = x.shape
         OH = (H + 2 * f.pad - f.k) // f.stride + 1; OW = (W + 2 * f.pad - f.k) // f.stride + 1
         out = torch.empty((B, OH, OW, f.cout), dtype=torch.float32, device=x.device)
-        flags = (_IN_SPLIT if f.split else 0) | (_OUT_SPLIT if out_split else 0)
+        flags = (_IN_SPLIT if f.split else 0) | (_OUT_SPLIT if out_split else 0) | (_W_TILED if tiled and f.wt is not None else 0)
         check(L.ssg_conv2d_nhwc_x(ptr(x), ptr(f.w), ptr(f.bias), ptr(res), ptr(out), B, H, W, f.cin, f.cout, f.k, f.k, f.stride, f.pad,
                                   1 if relu else 0, flags, f.acc_scale, ptr(getattr(f, "cscale", None)), ptr(ovf), stream()), "ssg_conv2d_nhwc_x")
         return out
 
     @staticmethod
-    def _conv_dual(L, o, x, c3, ds, out_split=False, ovf=None):
+    def _conv_dual(L, o, x, c3, ds, out_split=False, ovf=None, tiled=False):
         """relu(conv3(o) + downsample(x)) as one GEMM (ssg_conv1x1_dual_nhwc_x)."""
         B, H, W, _ = o.shape
         _, H2, W2, _ = x.shape
         out = torch.empty((B, H, W, c3.cout), dtype=torch.float32, device=o.device)
-        flags = (_IN_SPLIT if ds.split else 0) | (_OUT_SPLIT if out_split else 0)
+        flags = (_IN_SPLIT if ds.split else 0) | (_OUT_SPLIT if out_split else 0) | (_W_TILED if tiled and ds.wt is not None else 0)
         check(L.ssg_conv1x1_dual_nhwc_x(ptr(o), ptr(x), ptr(ds.w), ptr(ds.bias), ptr(out), B, H, W, c3.cin, H2, W2, ds.cin, ds.stride, c3.cout, 1,
                                         flags, ds.acc_scale, ptr(getattr(ds, "cscale", None)), ptr(ovf), stream()), "ssg_conv1x1_dual_nhwc_x")
         return out
@@ -493,6 +517,7 @@ class ResNet:
         L = _lib.lib()
         net = self._prepare()
         sp = net["split"]
+        tw = bool(getattr(self, "tiled_weights", True))
         x = x.to(self.device, torch.float32).contiguous()
         B, C, H, W = x.shape
         if C != 3:
@@ -530,20 +555,20 @@ class ResNet:
                 if fused is not None:
                     y = fused
                     continue
-                o = self._conv(L, y, blk["c1"], out_split=sp, ovf=ovf)
-                r = y if blk["ds"] is None else self._conv(L, y, blk["ds"], relu=False, out_split=sp, ovf=ovf)
-                y = self._conv(L, o, blk["c2"], res=r, relu=True, out_split=sp, ovf=ovf)
+                o = self._conv(L, y, blk["c1"], out_split=sp, ovf=ovf, tiled=tw)
+                r = y if blk["ds"] is None else self._conv(L, y, blk["ds"], relu=False, out_split=sp, ovf=ovf, tiled=tw)
+                y = self._conv(L, o, blk["c2"], res=r, relu=True, out_split=sp, ovf=ovf, tiled=tw)
                 continue
             if sp:
                 fused = self._bottleneck(L, y, blk, ovf)
                 if fused is not None:
                     y = fused
                     continue
-            o = o1_next if o1_next is not None else self._conv(L, y, blk["c1"], out_split=sp, ovf=ovf)
+            o = o1_next if o1_next is not None else self._conv(L, y, blk["c1"], out_split=sp, ovf=ovf, tiled=tw)
             o1_next = None
-            o = self._conv(L, o, blk["c2"], out_split=sp, ovf=ovf)
+            o = self._conv(L, o, blk["c2"], out_split=sp, ovf=ovf, tiled=tw)
             if blk["ds"] is not None:
-                y = self._conv_dual(L, o, y, blk["c3"], blk["ds"], out_split=sp, ovf=ovf)
+                y = self._conv_dual(L, o, y, blk["c3"], blk["ds"], out_split=sp, ovf=ovf, tiled=tw)
                 continue
             nxt = blocks[bi + 1]["c1"] if bi + 1 < len(blocks) else None
             Bo, Ho, Wo, _ = o.shape
@@ -551,7 +576,7 @@ class ResNet:
                     and L.ssg_conv_pair_supported(blk["c3"].cin, blk["c3"].cout, nxt.cout)):
                 y, o1_next = self._conv_pair(L, o, blk["c3"], y, nxt, ovf)
             else:
-                y = self._conv(L, o, blk["c3"], res=y, relu=True, out_split=sp, ovf=ovf)
+                y = self._conv(L, o, blk["c3"], res=y, relu=True, out_split=sp, ovf=ovf, tiled=tw)
         return y, sp
 
     @staticmethod

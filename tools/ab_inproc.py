@@ -3,7 +3,8 @@
 variant, round-robin, with HIP events around every C-ABI launch -- run-to-run and box-to-box noise (+-3 %, DVFS) is common to the variants.
 
 usage: ab_inproc.py [--B 1000] [--reps 6] name=lib.so[,ENV=VAL,...] ...
-Each variant gets its own dlopen'ed copy of the library (its `static` knob caches are read under its own environment at the first call)."""
+Each variant gets its own dlopen'ed copy of the library (its `static` knob caches are read under its own environment at the first call).
+Compile-time knobs (`-DSSG_CONV_WT=0`: row-major weight stages, `-DSSG_DMA_BPOS=...`) are compared as two builds of csrc/ssg_hip.hip."""
 import argparse
 import ctypes
 import os
