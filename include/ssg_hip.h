@@ -827,7 +827,7 @@ int ssg_oim_update_f32(const float* x, int64_t ldx, const int64_t* target, float
  *   folded and packed on its own, Kp = Cin1 + Cin2 with the first source first, one row scale over the whole row,
  *   bias = float32(b1) + float32(b2) added in float32.
  * One workgroup per output row, no atomics, no workspace, no host read.  Refused (-1) before any launch, outputs untouched: Cout % 64
- * != 0, Cin % 32 != 0 other than the stem's 3 (never in _dual), a packed row longer than ssg_fold_max_k() floats, a _dual source that is
+ * != 0 other than 32 (the InceptionNet stem layers), Cin % 32 != 0 other than the stem's 3 (never in _dual), a packed row longer than ssg_fold_max_k() floats, a _dual source that is
  * not 1x1, a NULL pointer, a negative stride, w_out not 16-byte aligned.  Non-finite parameters are not refused: they propagate by
  * IEEE rules into w' and bias, and a row whose maximum is Inf or NaN gets e = -40. */
 int ssg_fold_max_k(void);
@@ -879,6 +879,29 @@ int ssg_ap_colsum_cfg_f64(const double* R, int N, double* cs, const int64_t* ctr
 int ssg_ap_iterate_f64(const double* S, double* A, double* R, double* cs, uint8_t* window, uint8_t* E, int64_t* ctrl, int N, double damping,
                        int convergence_iter, int it0, int count, ssg_stream_t stream);
 int ssg_ap_finish_f64(const double* S, const uint8_t* E, int N, int32_t* I, int32_t* c, double* sums, int64_t* ctrl, ssg_stream_t stream);
+
+/* ---- InceptionNet embedder (reid/models/inception.py:50-119; ssg_amd/inception.py; csrc/inception.hip) ------------------------------
+ * The layers the ResNet entry points above do not cover.  Tensors are NHWC, fp32 or h8l8 containers as above.  Every output may be a
+ * CHANNEL SLICE of a wider tensor: out points at the first channel of the slice and out_ld is the number of floats (containers) between
+ * two pixels of that tensor (out_ld = the layer's own channel count writes a dense tensor); out_ld and the slice offset are multiples of
+ * 8 channels (pools on fp32: 4), nothing outside the slice is written -- the branches of a block land where torch.cat would put them.
+ * No tensor may exceed 2 GiB (SSG_ERR_INVALID, as ssg_conv2d_nhwc_x).
+ * ssg_inc_conv2d_nhwc_x: ssg_conv2d_nhwc_x without a residual for Cout % 32 == 0 (the 32-channel stem layers included): K x K = 1x1 or
+ *   3x3, stride 1 or 2, pad 0 or 1; Cin % 32 == 0 with w [Cout][K*K*Cin], or Cin == 4 (3x3 only: RGB0 pixels of ssg_nchw_to_nhwc4 /
+ *   _h4l4, w [Cout][64]) in ssg_conv2d_nhwc_x's reduction order.  flags: SSG_CONV_IN_SPLIT (in and w split halves, w rows pre-multiplied
+ *   by powers of two that ch_scale undoes; ch_scale is then required), SSG_CONV_OUT_SPLIT (out h8l8; *overflow = 1 when a value does not
+ *   fit).  out = [relu](acc * ch_scale + bias).  One wave per 64 pixels x 32 (Cout % 64: 64) channels, operands read straight from memory.
+ * ssg_inc_maxpool_nhwc_x: MaxPool2d(k, stride, pad), k <= 3, stride <= 2, 2 * pad <= k: OH = (H + 2 pad - k) / stride + 1; padding never
+ *   wins.  Exact (h8l8: the maximum of the decoded values, encoded again).  C % 4 == 0 (h8l8: 8).
+ * ssg_inc_avgpool3_nhwc_x: AvgPool2d(3, 1, 1), count_include_pad: the float32 sum of the nine taps in row-major order (rows outer) from
+ *   +0, taps outside the map add nothing, then one float32 division by 9 (h8l8: taps decoded, quotient encoded).
+ * ssg_inc_head_finish: x, out [rows, C] (out may be x): mode 0 out = relu(x); mode 1 out = x / max(||x||_2, 1e-12) (F.normalize). */
+int ssg_inc_conv2d_nhwc_x(const void* in, const void* w, const float* bias, void* out, int B, int H, int W, int Cin, int Cout, int K, int stride,
+                          int pad, int relu, int flags, const float* ch_scale, int out_ld, int32_t* overflow, ssg_stream_t stream);
+int ssg_inc_maxpool_nhwc_x(const void* in, void* out, int B, int H, int W, int C, int k, int stride, int pad, int split, int out_ld,
+                           ssg_stream_t stream);
+int ssg_inc_avgpool3_nhwc_x(const void* in, void* out, int B, int H, int W, int C, int split, int out_ld, ssg_stream_t stream);
+int ssg_inc_head_finish(const float* x, float* out, int rows, int C, int mode, ssg_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -82,7 +82,10 @@ def __getattr__(name):   # lazy: torch import only when the compute surface is t
     if name in ("DECFinedTrainer2Mixin", "DECJointTrainer2Mixin"):
         from . import trainers
         return getattr(trainers, name)
-    if name in ("create", "names", "ResNet", "synthetic_state_dict"):
+    if name in ("create", "names", "InceptionNet"):      # the model factory with all six names (reid/models/__init__.py)
+        from . import inception
+        return getattr(inception, name)
+    if name in ("ResNet", "synthetic_state_dict"):
         from . import resnet
         return getattr(resnet, name)
     raise AttributeError(name)

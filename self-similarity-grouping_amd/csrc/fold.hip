@@ -158,8 +158,9 @@ using namespace ssg;
 
 // shape rules of one source -> its packed length in *K; the error names the entry point
 int fold_check_source(const char* fn, const char* which, int Cout, int Cin, int KH, int KW, bool allow_stem, int* K) {
-  if (Cout <= 0 || Cout % 64 || Cin <= 0 || KH <= 0 || KW <= 0 || KH > 64 || KW > 64 || !(Cin % 32 == 0 || (allow_stem && Cin == 3))) {
-    ssg_set_error("%s: unsupported shape (%s: Cout=%d Cin=%d KH=%d KW=%d): Cout %% 64 == 0 and Cin %% 32 == 0%s are needed", fn, which, Cout, Cin, KH, KW,
+  // (Cout == 32: the InceptionNet stem layers, csrc/inception.hip)
+  if (Cout <= 0 || (Cout % 64 && Cout != 32) || Cin <= 0 || KH <= 0 || KW <= 0 || KH > 64 || KW > 64 || !(Cin % 32 == 0 || (allow_stem && Cin == 3))) {
+    ssg_set_error("%s: unsupported shape (%s: Cout=%d Cin=%d KH=%d KW=%d): Cout %% 64 == 0 (or Cout == 32) and Cin %% 32 == 0%s are needed", fn, which, Cout, Cin, KH, KW,
                   allow_stem ? " (or Cin == 3, the stem)" : "");
     return SSG_ERR_INVALID;
   }

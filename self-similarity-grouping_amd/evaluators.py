@@ -16,6 +16,7 @@ from collections import OrderedDict
 
 import torch
 
+from .inception import InceptionNet
 from .resnet import ResNet
 
 
@@ -32,7 +33,9 @@ def extract_cnn_feature(model, inputs, for_eval, modules=None):
         raise NotImplementedError("forward hooks (cnn.py:24-35) are not part of the grouping path")
     model.eval()
     with torch.no_grad():
-        outputs = model(torch.as_tensor(inputs), for_eval)[0]
+        outputs = model(torch.as_tensor(inputs), for_eval)
+    if not isinstance(getattr(model, "module", model), InceptionNet):
+        outputs = outputs[0]        # (InceptionNet returns its one tensor, whatever for_eval says: inception.py:90-119)
     if isinstance(outputs, list):
         return [x.data.cpu() for x in outputs]
     return outputs.data.cpu()
@@ -40,8 +43,8 @@ def extract_cnn_feature(model, inputs, for_eval, modules=None):
 
 def _check_model(model):
     m = getattr(model, "module", model)
-    if not isinstance(m, ResNet):
-        raise TypeError("ssg_amd.extract_features drives ssg_amd.resnet.ResNet embedders (HIP kernels); got %r" % type(model))
+    if not isinstance(m, (ResNet, InceptionNet)):
+        raise TypeError("ssg_amd.extract_features drives ssg_amd.resnet.ResNet / ssg_amd.inception.InceptionNet embedders (HIP kernels); got %r" % type(model))
     return m
 
 

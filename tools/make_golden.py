@@ -270,6 +270,47 @@ def embed_fixture_basic():
     return ok
 
 
+def embed_fixture_inception():
+    """Embedding golden of the InceptionNet embedder: the REAL reference model (reid.models.create('inception', ...)) under the stub
+    modules of import_reid(), loaded strictly with the build's seeded synthetic weights (which pins key names, order and shapes), on
+    4 seeded 144 x 56 images (selftraining.py:105) -> tests/golden/embed_inception_ref.npz: model(x) for num_features=256 with norm
+    False / True and for num_features=0, and evaluators.py:41-43 (the sum of both orientations under one L2 norm) on the default
+    model -- stated here, because reid.evaluators.extract_features cannot drive this model (cnn.py:16 passes for_eval to a forward
+    that does not take it).  tests/inception_ref.py is checked against every output."""
+    import torch
+    from ssg_amd import inception
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import inception_ref
+    reid = import_reid()
+    torch.manual_seed(0)
+    imgs = torch.randn(4, 3, 144, 56, generator=torch.Generator().manual_seed(1))
+    ok = True
+    rec = {}
+    for tag, nf, norm in (("f256", 256, False), ("f256_norm", 256, True), ("f0", 0, False)):
+        model = reid.models.create('inception', num_features=nf, norm=norm)
+        sd = inception.synthetic_state_dict(seed=1, num_features=nf)
+        res = model.load_state_dict(sd, strict=True)
+        assert not res.unexpected_keys and not res.missing_keys, res
+        assert list(model.state_dict().keys()) == list(sd.keys()), "key order"
+        model.eval()
+        with torch.no_grad():
+            ref = model(imgs)
+            mine = inception_ref.forward(sd, imgs, norm)
+            outs = [("model_" + tag, ref, mine)]
+            if tag == "f256":
+                both = ref + model(reid.evaluators.fliplr(imgs))                     # evaluators.py:41-43
+                both = both.div(torch.norm(both, p=2, dim=1, keepdim=True).expand_as(both))
+                outs.append(("embed_with_flip_f256", both, inception_ref.embed_with_flip(sd, imgs)))
+                rec["keys"] = np.array(inception_ref.key_listing(model.state_dict()))
+        for name, r, m in outs:
+            err = (r - m).abs().max().item()
+            print("inception %s: torch-restatement vs reference max|diff| = %.3e  (|max| %.3e)" % (name, err, r.abs().max().item()))
+            ok = ok and err < 1e-6
+            rec[name] = r.numpy()
+    np.savez_compressed(os.path.join(OUT, "embed_inception_ref.npz"), image_seed=1, weight_seed=1, **rec)
+    return ok
+
+
 def eval_fixture():
     """Retrieval metrics (reid/evaluators.py:88-129 evaluate_all -> reid/evaluation_metrics/ranking.py cmc, mean_ap with
     sklearn's average_precision_score): random query x gallery float32 distance blocks with Market-like id / camera
@@ -691,6 +732,10 @@ def main():
         sys.exit(0 if ok else 1)
     if "--only-embed-basic" in sys.argv:  # regenerate just tests/golden/embed_basic_ref.npz
         ok = embed_fixture_basic()
+        print("ALL OK" if ok else "ORACLE MISMATCH")
+        sys.exit(0 if ok else 1)
+    if "--only-embed-inception" in sys.argv:  # regenerate just tests/golden/embed_inception_ref.npz
+        ok = embed_fixture_inception()
         print("ALL OK" if ok else "ORACLE MISMATCH")
         sys.exit(0 if ok else 1)
     if "--only-eval" in sys.argv:         # regenerate just tests/golden/eval_cases.npz

@@ -62,3 +62,35 @@ def checkpoint_like_state_dict(seed):
             sd[p + "running_mean"] = 0.1 * torch.randn(n, generator=g)
             sd[p + "bias"] = 0.05 * torch.randn(n, generator=g)
     return sd
+
+
+def checkpoint_like_inception_state_dict(seed, num_features=256):
+    """`checkpoint_like_state_dict` for the InceptionNet embedder (ssg_amd.inception.synthetic_state_dict): the same draw for every
+    BatchNorm2d behind a convolution; `feat_bn` gets a milder spread (scales over one decade) and `feat.bias` is non-zero, so that
+    the folded Linear of the head is exercised too."""
+    import torch
+    from ssg_amd import inception
+    sd = inception.synthetic_state_dict(seed=seed, num_features=num_features)
+    g = torch.Generator().manual_seed(seed + 100)
+    for k in list(sd):
+        if not k.endswith("running_var"):
+            continue
+        p = k[: -len("running_var")]
+        n = sd[k].numel()
+        if p.startswith("feat_bn"):
+            var = torch.exp(torch.empty(n).uniform_(float(np.log(1e-7)), float(np.log(1e-5)), generator=g))
+            s = torch.exp(0.5 * torch.randn(n, generator=g)) * 30.0
+            sd[p + "running_var"] = var
+            sd[p + "weight"] = s * torch.sqrt(var + 1e-5)
+            sd[p + "running_mean"] = 3e-3 * torch.randn(n, generator=g)
+            sd[p + "bias"] = 0.05 * torch.randn(n, generator=g)
+            sd["feat.bias"] = 1e-3 * torch.randn(n, generator=g)
+            continue
+        var = torch.exp(torch.empty(n).uniform_(float(np.log(1e-3)), float(np.log(1e2)), generator=g))
+        s = torch.exp(2.3 * torch.randn(n, generator=g))
+        s = s / s.pow(2).mean().sqrt()
+        sd[p + "running_var"] = var
+        sd[p + "weight"] = s * torch.sqrt(var + 1e-5)
+        sd[p + "running_mean"] = 0.1 * torch.randn(n, generator=g)
+        sd[p + "bias"] = 0.05 * torch.randn(n, generator=g)
+    return sd
