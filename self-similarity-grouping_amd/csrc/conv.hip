@@ -566,11 +566,19 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64, (BM / WM) * (BN / WN) =
 // quarter fewer LDS bytes per MFMA), half the waves at every barrier, 2 waves per SIMD with up to 256 VGPRs each.  TWOSET: the fragments
 // of k-tile t + 1 are read into a second register set right after the barrier that publishes them, under the last MFMA group of tile t
 // (source_bound_dma_kernel's schedule).
-template <int BN, bool ONEPROD = false, int BM = 128, bool DUAL = false, int NS = 3, int WM_ = 64, bool TWOSET = false>
+// LINE: fetch order of the pixel operand.  0 = one k-tile (64 bytes per pixel row) per step; 1 = the two k-tiles of a 32-channel run, i.e. both
+// halves of a 128-byte line, requested back to back at every other step (same stages, same multiply order: bit-identical).  Needs an even
+// number of k-tiles and runs of 32 channels in both inputs -- the launchers check it (conv_line_order).
+#ifndef SSG_DMA_BPOS
+#define SSG_DMA_BPOS 2
+#endif
+template <int BN, bool ONEPROD = false, int BM = 128, bool DUAL = false, int NS = 3, int WM_ = 64, bool TWOSET = false, int LINE = 0>
 __global__ __launch_bounds__((BM / WM_) * (BN / 64) * 64, BM == 256 ? 1 : (BN == 256 ? 4 : 3)) void conv_dma_kernel(ConvParams p) {   // 4 (3) waves per SIMD: at most 128 (168) VGPRs
   static_assert(NS == 3 || NS == 4, "three or four stages");
   static_assert(WM_ == 64 || (WM_ == 128 && BM == 256 && BN == 256 && !ONEPROD && NS == 4), "128-row wave tiles: the 256 x 256 three-product kernel");
   static_assert(!TWOSET || WM_ == 128, "second fragment set: 8-wave kernel only");
+  static_assert(LINE == 0 || (LINE == 1 && !ONEPROD && !TWOSET), "line order: three-product kernels with one fragment set");
+  constexpr int LN = SSG_DMA_BPOS > 0 ? LINE : 0;                   // (A/B builds with the barrier in front of the multiply keep the k-tile order)
   constexpr int WM = WM_, WN = 64, MT = WM / 32, NT = 2, CBK = 16;
   constexpr int WCOLS = BN / WN, NW = (BM / WM) * WCOLS;             // 8 waves (2 x 4) for 128 x 256, 4 waves (2 x 2) for 128 x 128, 16 (4 x 4) for 256 x 256
   constexpr int ABLK = BM / 16 / NW, WBLK = BN / 16 / NW;            // 16-row A / W blocks per wave and stage: 1 or 2
@@ -626,6 +634,7 @@ __global__ __launch_bounds__((BM / WM_) * (BN / 64) * 64, BM == 256 ? 1 : (BN ==
   // (clamped at the last tile), so the tap decode is a few scalar increments instead of two integer divisions per tile and wave,
   // and a lane's address is its tap-(0,0) offset + one uniform delta (out-of-range taps: the offset is replaced, not clamped).
   int dn = 0, dr = 0, ds = 0, dch = 0;
+  [[maybe_unused]] int dnw = 0;                                     // LINE = 1: the weight cursor (dn is then the even tile of the next pixel pair)
 #ifndef SSG_DMA_AUX_A
 #define SSG_DMA_AUX_A 0        /* cache policy of the activation DMA (2 = nt): A/B knob, measured neutral */
 #endif
@@ -657,6 +666,43 @@ __global__ __launch_bounds__((BM / WM_) * (BN / 64) * 64, BM == 256 ? 1 : (BN ==
       const int w1_ = ds == p.KW ? 1 : 0; ds = w1_ ? 0 : ds; dr += w1_;                                               \
       const int w2_ = dr == p.KH ? 1 : 0; dr = w2_ ? 0 : dr; dch += w2_;                                              \
     }                                                                                                                \
+  }
+  // LINE = 1: the pixel pieces of k-tiles dn (even) and dn + 1 -- the two 64-byte halves of one 128-byte line per pixel row -- are requested
+  // back to back, into the stages STE / STO of the two tiles (same tap, same 32-channel chunk: one padding predicate, the second offset is
+  // the first + 64).  The weight cursor dnw moves on its own, one k-tile per step as before.  Both clamp at the end: the tail re-fetches the
+  // last pair / the last weight tile into stages nobody reads again, which keeps the vmcnt accounting uniform.
+#define SSG_DMA_A2(J, STE, STO)                                                                                      \
+  {                                                                                                                  \
+    unsigned aoff;                                                                                                   \
+    if (!DUAL || dn < nkA) {                                                                                          \
+      const bool ok = ab##J >= 0 && (unsigned)(ah##J + dr) < (unsigned)p.H && (unsigned)(aw##J + ds) < (unsigned)p.W;  \
+      aoff = ok ? (unsigned)(abase##J + ddelta_) : 0x80000000u;                                                       \
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(in_rsrc, SSG_LDSP(STE + (wave * ABLK + J) * 1024), 16, aoff, 0, 0, SSG_DMA_AUX_A);        \
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(in_rsrc, SSG_LDSP(STO + (wave * ABLK + J) * 1024), 16, aoff + 64u, 0, 0, SSG_DMA_AUX_A);  \
+    } else {                                                                                                          \
+      aoff = a2b##J + (unsigned)((dn - nkA) * CBK * 4);                                                                \
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(in2_rsrc, SSG_LDSP(STE + (wave * ABLK + J) * 1024), 16, aoff, 0, 0, SSG_DMA_AUX_A);       \
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(in2_rsrc, SSG_LDSP(STO + (wave * ABLK + J) * 1024), 16, aoff + 64u, 0, 0, SSG_DMA_AUX_A); \
+    }                                                                                                                 \
+  }
+#define SSG_DMA_PAIR(STE, STO)                                                                                       \
+  {                                                                                                                  \
+    const int ddelta_ = ((dr * p.W + ds) * p.Cin + dch * 32) * 4;                                                     \
+    SSG_DMA_A2(0, STE, STO) if (ABLK == 2) SSG_DMA_A2(1, STE, STO)                                                    \
+    {                                                                                                                \
+      const int adv_ = dn < nk - 2 ? 1 : 0;                                                                          \
+      dn += 2 * adv_;                                                                                                \
+      ds += adv_;                                                                                                    \
+      const int w1_ = ds == p.KW ? 1 : 0; ds = w1_ ? 0 : ds; dr += w1_;                                               \
+      const int w2_ = dr == p.KH ? 1 : 0; dr = w2_ ? 0 : dr; dch += w2_;                                              \
+    }                                                                                                                \
+  }
+#define SSG_DMA_W(ST)                                                                                                \
+  {                                                                                                                  \
+    const unsigned kb_ = (unsigned)dnw << wkshift;                                                                    \
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rsrc, SSG_LDSP(ST + BM * 64 + wave * (1024 * WBLK)), 16, wo0 + kb_, 0, 0, SSG_DMA_AUX_W);   \
+    if (WBLK == 2) __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rsrc, SSG_LDSP(ST + BM * 64 + wave * 2048 + 1024), 16, wo1 + kb_, 0, 0, SSG_DMA_AUX_W); \
+    dnw += dnw < nk - 1 ? 1 : 0;                                                                                     \
   }
 
   // ---- fragment addressing: lane (row l32 of a 32-row MFMA tile, k half h); swizzle g = (row>>2)&3 depends on l32 only
@@ -712,9 +758,6 @@ __global__ __launch_bounds__((BM / WM_) * (BN / 64) * 64, BM == 256 ? 1 : (BN ==
   // remaining MFMAs of the tile are still queued behind the barrier: the matrix pipe has work while the next tile's fragment reads are
   // in flight (with the barrier in front of the whole multiply every wave of the CU read LDS at the same time and the pipes drained).
   // All NS stages are in flight ahead of the first tile; the DMA of tile t + NS goes into the stage of tile t right after the barrier.
-#ifndef SSG_DMA_BPOS
-#define SSG_DMA_BPOS 2
-#endif
   constexpr int BPOS = ONEPROD ? 0 : SSG_DMA_BPOS;
   constexpr int TDMA = ABLK + WBLK;                                  // DMA instructions per wave and tile
   const int nfull = nk / NS * NS;
@@ -841,6 +884,52 @@ __global__ __launch_bounds__((BM / WM_) * (BN / 64) * 64, BM == 256 ? 1 : (BN ==
       SSG_G3                                                                                                         \
       SSG_PRIO(0) }
 #define SSG_LAST(ST) { SSG_READS(ST) SSG_G1 SSG_G2 SSG_G3 }
+    if constexpr (LN == 1) {
+    // Line order.  Step t multiplies tile t out of stage t % NS (ST), publishes tile t + 1 and then issues the weights of tile t + NS into ST
+    // and, at every other step (PAIR: t odd for NS = 4, t even for NS = 3, so that t + NS - 1 is even), the pixel pieces of tiles t + NS - 1
+    // and t + NS into the previous stage STP (free since step t - 1) and ST.  The even tile of a pair is requested NS - 2 steps before it is
+    // published instead of NS - 1; the odd tile as before.
+    // vmcnt literal = DMA instructions issued after the youngest one tile t + 1 needs.  Per tile A = ABLK pixel and W = WBLK weight
+    // instructions; a step issues [pair] weights, and a pair goes out block by block (even, odd half of block 0, then of block 1), so the
+    // last instruction of an EVEN tile has one pair instruction behind it, whatever ABLK:
+    //   NS = 4, t even (no pair):  ... | A(t) A(t+1) W(t+1)* | W(t+2) | A(t+2) A(t+3) W(t+3) ||          -> 2 A + 2 W
+    //   NS = 4, t odd  (pair):     ... | W(t+1) | A(t+1)* A(t+2) W(t+2) | W(t+3) ||                      -> 1 + 2 W
+    //   NS = 3, t even (pair):     ... | A(t) A(t+1) W(t+1)* | W(t+2) ||                                 -> W
+    //   NS = 3, t odd  (no pair):  ... | W(t+1) | A(t+1)* A(t+2) W(t+2) ||                               -> 1 + W
+    // The prologue issues the steps t = -NS ... -1 of the same schedule, so the literals hold from t = 0 on.
+    constexpr int VM_PAIR = NS == 4 ? 1 + 2 * WBLK : WBLK, VM_NONE = NS == 4 ? 2 * ABLK + 2 * WBLK : 1 + WBLK;
+#define SSG_LSTEP(STP, ST, PAIR)                                                                                     \
+    { SSG_READS(ST)                                                                                                  \
+      SSG_G1                                                                                                         \
+      if constexpr (BPOS == 2) SSG_G2                                                                                \
+      __builtin_amdgcn_sched_barrier(0);                                                                             \
+      asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"((PAIR) ? VM_PAIR : VM_NONE) : "memory");       \
+      if constexpr ((PAIR) != 0) SSG_DMA_PAIR(STP, ST)                                                               \
+      SSG_DMA_W(ST)                                                                                                  \
+      __builtin_amdgcn_sched_barrier(0);                                                                             \
+      if constexpr (BPOS == 1) SSG_G2                                                                                \
+      SSG_G3 }
+    if constexpr (NS == 4) {
+      SSG_DMA_W(st0)
+      SSG_DMA_PAIR(st0, st1) SSG_DMA_W(st1)
+      SSG_DMA_W(st2)
+      SSG_DMA_PAIR(st2, st3) SSG_DMA_W(st3)
+      asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(1 + 2 * ABLK + 3 * WBLK) : "memory");   // W(0) A(0) landed for everybody
+      int kt = 0;
+      for (; kt + 4 <= nk; kt += 4) { SSG_LSTEP(st3, st0, 0) SSG_LSTEP(st0, st1, 1) SSG_LSTEP(st1, st2, 0) SSG_LSTEP(st2, st3, 1) }
+      if (nk - kt >= 2) { SSG_LSTEP(st3, st0, 0) SSG_LSTEP(st0, st1, 1) }       // nk is even: full steps, their fetches are the clamped ones
+    } else {
+      SSG_DMA_W(st0)
+      SSG_DMA_PAIR(st0, st1) SSG_DMA_W(st1)
+      SSG_DMA_W(st2)
+      asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(1 + 2 * WBLK) : "memory");          // W(0) A(0) landed for everybody
+      int kt = 0;                             // six steps per trip: stage and parity of a step are compile-time
+      for (; kt + 6 <= nk; kt += 6) { SSG_LSTEP(st2, st0, 1) SSG_LSTEP(st0, st1, 0) SSG_LSTEP(st1, st2, 1) SSG_LSTEP(st2, st0, 0) SSG_LSTEP(st0, st1, 1) SSG_LSTEP(st1, st2, 0) }
+      if (nk - kt >= 2) { SSG_LSTEP(st2, st0, 1) SSG_LSTEP(st0, st1, 0) }
+      if (nk - kt >= 4) { SSG_LSTEP(st1, st2, 1) SSG_LSTEP(st2, st0, 0) }
+    }
+#undef SSG_LSTEP
+    } else {
     SSG_DMA_NEXT(st0)
     SSG_DMA_NEXT(st1)
     SSG_DMA_NEXT(st2)
@@ -858,6 +947,7 @@ __global__ __launch_bounds__((BM / WM_) * (BN / 64) * 64, BM == 256 ? 1 : (BN ==
     if (nk - nfull >= 1) SSG_LAST(st0)
     if (nk - nfull >= 2) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory"); SSG_LAST(st1) }
     if constexpr (NS == 4) { if (nk - nfull == 3) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory"); SSG_LAST(st2) } }
+    }
 #undef SSG_READS
 #undef SSG_G1
 #undef SSG_G2
@@ -871,6 +961,9 @@ __global__ __launch_bounds__((BM / WM_) * (BN / 64) * 64, BM == 256 ? 1 : (BN ==
 #undef SSG_PUBLISH
 #undef SSG_DMA_NEXT
 #undef SSG_DMA_A
+#undef SSG_DMA_PAIR
+#undef SSG_DMA_A2
+#undef SSG_DMA_W
 #undef SSG_MMA
 #pragma unroll
   for (int i = 0; i < MT; i++)
@@ -1222,6 +1315,23 @@ static int launch_conv_bk(const ConvParams& p, hipStream_t stream) {
   hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WM, WN, CIN4, CBK, SPLIT>), dim3(tiles), dim3((BM / WM) * (BN / WN) * 64), lds, stream, p);
   return ssg_check_hip(hipGetLastError(), "conv_igemm_kernel");
 }
+// Fetch order of conv_dma_kernel's pixel operand (its template parameter LINE) for one launch.  The line order needs an even number of
+// k-tiles and 32-channel runs in both inputs (every shape the two convolution entry points accept has them; the distance GEMMs of the
+// source term come with any multiple of 16 and keep the k-tile order, as does the one-product bound pass).  SSG_CONV_LINE=0 / 1 forces the
+// order for every launch that can take it; unset, each instance runs the order that measured faster.
+enum ConvDmaInst { DMA_128 = 0, DMA_WIDE, DMA_WIDE_DUAL, DMA_TALL, DMA_TALL_DUAL };
+static int conv_line_order(const ConvParams& p, ConvDmaInst inst) {
+  static int knob = -2;
+  if (knob == -2) { const char* e = getenv("SSG_CONV_LINE"); knob = e ? (atoi(e) == 1 ? 1 : 0) : -1; }
+  if (p.products != 3 || p.epi != 0 || ((p.Kpad / 16) & 1) || (p.Cin % 32) || (p.in2 && (p.Cin2 % 32))) return 0;
+  if (knob >= 0) return knob;
+  // forward of 1000 images, both orders interleaved in one process (profiles/r08_ab_conv_line_fetch.txt): 128 x 128 - 3 / - 6 %, 128 x 256
+  // with a residual - 3 %, DUAL 0 ... - 2 %, 256 x 256 1x1 0 ... - 4 % and 3x3 - 5 %; the 256 x 256 DUAL instance (behind SSG_CONV_TALL_DUAL)
+  // was not timed and keeps the k-tile order
+  static const int dflt[5] = {1, 1, 1, 1, 0};
+  return dflt[inst];
+}
+
 // BK=16 stages (default): half the LDS of BK=32 -> 3 instead of 2 co-resident workgroups per CU, so one
 // workgroup's prologue / epilogue overlaps the others' MFMA phases.  The fused dual-input GEMM stays
 // on BK=32.  SSG_CONV_BK16_MAXK=<K> restricts BK=16 to reductions of at most K (tuning knob).
@@ -1242,7 +1352,8 @@ static int launch_conv(const ConvParams& p, hipStream_t stream, bool split = fal
         if (dma < 0) { const char* e = getenv("SSG_CONV_DMA"); dma = e ? atoi(e) : 3; }
         if ((dma & 2) && p.epi == 0 && !p.in2) {
           const int tiles = ((p.M + 127) / 128) * (p.Cout / 128);
-          hipLaunchKernelGGL(conv_dma_kernel<128>, dim3(tiles), dim3(256), 0, stream, p);
+          if (conv_line_order(p, DMA_128)) hipLaunchKernelGGL((conv_dma_kernel<128, false, 128, false, 3, 64, false, 1>), dim3(tiles), dim3(256), 0, stream, p);
+          else hipLaunchKernelGGL(conv_dma_kernel<128>, dim3(tiles), dim3(256), 0, stream, p);
           return ssg_check_hip(hipGetLastError(), "conv_dma_kernel<128>");
         }
       }
@@ -1279,7 +1390,8 @@ static int launch_conv_wide(const ConvParams& p, hipStream_t stream) {
     static int tall_dual = -1;               // SSG_CONV_TALL_DUAL=1: also for the fused conv3 | downsample GEMMs (tuning knob)
     if (tall_dual < 0) { const char* e = getenv("SSG_CONV_TALL_DUAL"); tall_dual = e ? atoi(e) : 0; }
     if (tall > 0 && p.products == 3 && p.epi == 0 && p.in2 && tall_dual && tiles_tall >= tall) {
-      hipLaunchKernelGGL((conv_dma_kernel<256, false, 256, true, 4>), dim3(tiles_tall), dim3(1024), 0, stream, p);
+      if (conv_line_order(p, DMA_TALL_DUAL)) hipLaunchKernelGGL((conv_dma_kernel<256, false, 256, true, 4, 64, false, 1>), dim3(tiles_tall), dim3(1024), 0, stream, p);
+      else hipLaunchKernelGGL((conv_dma_kernel<256, false, 256, true, 4>), dim3(tiles_tall), dim3(1024), 0, stream, p);
       return ssg_check_hip(hipGetLastError(), "conv_dma_kernel<256x256, dual>");
     }
     static int tall_res = -1;                // SSG_CONV_TALL_RES=1: also for convolutions with a residual epilogue (tuning knob)
@@ -1291,13 +1403,16 @@ static int launch_conv_wide(const ConvParams& p, hipStream_t stream) {
       if (tall_wm < 0) { const char* e = getenv("SSG_CONV_TALL_WM"); tall_wm = e ? atoi(e) : 64; }
       if (tall_wm == 128) hipLaunchKernelGGL((conv_dma_kernel<256, false, 256, false, 4, 128, false>), dim3(tiles_tall), dim3(512), 0, stream, p);
       else if (tall_wm == 129) hipLaunchKernelGGL((conv_dma_kernel<256, false, 256, false, 4, 128, true>), dim3(tiles_tall), dim3(512), 0, stream, p);
+      else if (tall_ns == 4 && conv_line_order(p, DMA_TALL)) hipLaunchKernelGGL((conv_dma_kernel<256, false, 256, false, 4, 64, false, 1>), dim3(tiles_tall), dim3(1024), 0, stream, p);
       else if (tall_ns == 4) hipLaunchKernelGGL((conv_dma_kernel<256, false, 256, false, 4>), dim3(tiles_tall), dim3(1024), 0, stream, p);
       else hipLaunchKernelGGL((conv_dma_kernel<256, false, 256, false>), dim3(tiles_tall), dim3(1024), 0, stream, p);
       return ssg_check_hip(hipGetLastError(), "conv_dma_kernel<256x256>");
     }
     const int tiles = ((p.M + 127) / 128) * (p.Cout / 256);
     if (p.products == 1) hipLaunchKernelGGL((conv_dma_kernel<256, true>), dim3(tiles), dim3(512), 0, stream, p);
+    else if (p.in2 && conv_line_order(p, DMA_WIDE_DUAL)) hipLaunchKernelGGL((conv_dma_kernel<256, false, 128, true, 3, 64, false, 1>), dim3(tiles), dim3(512), 0, stream, p);
     else if (p.in2) hipLaunchKernelGGL((conv_dma_kernel<256, false, 128, true>), dim3(tiles), dim3(512), 0, stream, p);
+    else if (conv_line_order(p, DMA_WIDE)) hipLaunchKernelGGL((conv_dma_kernel<256, false, 128, false, 3, 64, false, 1>), dim3(tiles), dim3(512), 0, stream, p);
     else hipLaunchKernelGGL(conv_dma_kernel<256>, dim3(tiles), dim3(512), 0, stream, p);
     return ssg_check_hip(hipGetLastError(), "conv_dma_kernel");
   }

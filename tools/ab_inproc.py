@@ -4,6 +4,7 @@ variant, round-robin, with HIP events around every C-ABI launch -- run-to-run an
 
 usage: ab_inproc.py [--B 1000] [--reps 6] name=lib.so[,ENV=VAL,...] ...
 Each variant gets its own dlopen'ed copy of the library (its `static` knob caches are read under its own environment at the first call).
+Run-time knobs are compared on ONE build (`new=lib.so line0=lib.so,SSG_CONV_LINE=0`: the pixel fetch order of conv_dma_kernel).
 Compile-time knobs (`-DSSG_CONV_WT=0`: row-major weight stages, `-DSSG_DMA_BPOS=...`) are compared as two builds of csrc/ssg_hip.hip."""
 import argparse
 import ctypes

@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdint>
+#include <cstdlib>
 #include <algorithm>
 
 #define LDSP(ptr_) ((__attribute__((address_space(3))) void*)(ptr_))
@@ -45,6 +46,52 @@ __global__ __launch_bounds__(NW * 64) void read_tiles(const unsigned char* A, in
       const int nx = kt + s + NS - 1;
       dma16(rs, lds0 + (unsigned)((s + NS - 1) % NS) * (BM * 64), off(nx < nk ? nx : nk - 1));
       asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(NS - 1) : "memory");
+      acc += *reinterpret_cast<const unsigned*>(&st[s][tid * 4 % (BM * 64)]);
+      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    }
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  if (acc == 0x12345678u) sink[0] = acc;
+}
+
+// line-fetch reader (row-major tensor only): the same four 64-byte k-tile stages, but the two halves of a 128-byte line are requested together.
+//   PAT 1: two 16-row x 64 B instructions back to back (k-tiles t, t + 1 into their two stages) at every even step, none at odd steps
+//   PAT 2: two 8-row x 128 B instructions (whole lines, 1 KB contiguous in LDS; the four stages seen as two pair buffers of 128 B rows)
+// A wave owns the same 16 rows either way.  At step t the stages of tiles t - 2 and t - 1 are free (second barrier of step t - 1).
+template <int PAT, int NW>
+__global__ __launch_bounds__(NW * 64) void read_lines(const unsigned char* A, int M, int nk, unsigned bytes, unsigned* sink) {
+  constexpr int BM = NW * 16;
+  __shared__ __attribute__((aligned(1024))) unsigned char st[4][BM * 64];
+  const int tid = (int)threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int tile = (int)blockIdx.x;
+  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(A), 0, bytes, 0x00020000);
+  const unsigned pitch = (unsigned)nk * 64u, ldsb = (unsigned)(uintptr_t)LDSP(&st[0][0]);
+  // PAT 1: lane = (row lane >> 2 of 16, 16-byte piece lane & 3 of a 64-byte half); PAT 2: lane = (row lane >> 3 of 8, piece lane & 7 of a line)
+  const int r1 = tile * BM + wave * 16 + (lane >> 2), r2 = tile * BM + wave * 16 + (lane >> 3);
+  const unsigned o1 = r1 < M ? (unsigned)r1 * pitch + (unsigned)(lane & 3) * 16u : 0x80000000u;
+  const unsigned o2a = r2 < M ? (unsigned)r2 * pitch + (unsigned)(lane & 7) * 16u : 0x80000000u;
+  const unsigned o2b = r2 + 8 < M ? o2a + 8u * pitch : 0x80000000u;
+  auto pair = [&](int t) {                                  // k-tiles t (even) and t + 1
+    const int tc = t < nk ? t : nk - 2;
+    if (PAT == 1) {
+      dma16(rs, ldsb + (unsigned)(t & 3) * (BM * 64) + (unsigned)wave * 1024u, o1 + (unsigned)tc * 64u);
+      dma16(rs, ldsb + (unsigned)((t + 1) & 3) * (BM * 64) + (unsigned)wave * 1024u, o1 + (unsigned)tc * 64u + 64u);
+    } else {
+      const unsigned pb = ldsb + (unsigned)((t >> 1) & 1) * (BM * 128) + (unsigned)wave * 2048u;
+      dma16(rs, pb, o2a + (unsigned)tc * 64u);
+      dma16(rs, pb + 1024u, o2b + (unsigned)tc * 64u);
+    }
+  };
+  pair(0);
+  unsigned acc = 0;
+  for (int kt = 0; kt < nk; kt += 4) {
+#pragma unroll
+    for (int s = 0; s < 4; s++) {
+      if ((s & 1) == 0) pair(kt + s + 2);
+      // tile t landed: even t -- the second half of its pair and the pair just issued are younger (PAT 2: its pair is ONE group of two
+      // instructions, the pair just issued is younger); odd t -- only the pair issued one step ago is younger
+      if (PAT == 1 && (s & 1) == 0) asm volatile("s_waitcnt vmcnt(3)\n\ts_barrier" ::: "memory");
+      else asm volatile("s_waitcnt vmcnt(2)\n\ts_barrier" ::: "memory");
       acc += *reinterpret_cast<const unsigned*>(&st[s][tid * 4 % (BM * 64)]);
       asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
     }
@@ -97,6 +144,16 @@ int main() {
   RD(0, 8, 3, "row-major NHWC (4 KB pixel pitch)")
   RD(1, 8, 3, "k-tile-major per tile (8 KB pieces)")
   RD(2, 8, 3, "32 x 32 blocks (4 KB pieces)")
+  // the two 64-byte halves of a 128-byte line: one k-tile apart (the RD(0, ...) rows above and (a) below), back to back (b), one instruction (c)
+#define RL(PAT, NW, NAME) { const float ms = best_of([&] { hipLaunchKernelGGL((read_lines<PAT, NW>), dim3((M + NW * 16 - 1) / (NW * 16)), dim3(NW * 64), 0, 0, A, M, nk, (unsigned)bytes, sink); }); \
+    printf("  read  %-44s %d-row tiles, 4 stages: %.3f ms  %.0f GB/s\n", NAME, NW * 16, ms, gb / ms * 1e3); }
+  RD(0, 16, 4, "(a) 16 rows x 64 B, halves one k-tile apart")
+  RL(1, 16, "(b) 16 rows x 64 B, halves back to back")
+  RL(2, 16, "(c) 8 rows x 128 B per instruction")
+  RD(0, 8, 4, "(a) 16 rows x 64 B, halves one k-tile apart")
+  RL(1, 8, "(b) 16 rows x 64 B, halves back to back")
+  RL(2, 8, "(c) 8 rows x 128 B per instruction")
+  if (getenv("TILE_STREAM_LINES_ONLY")) return 0;          // (the one-counter pass over the three patterns)
   SHARED = 1;
   RD(0, 16, 4, "row-major [Cout][K] (4 KB row pitch)")
   RD(1, 16, 4, "k-tile-major (16 KB pieces)")
