@@ -196,8 +196,9 @@ extern "C" int ssg_source_rowmin_filtered(const float* tgt, const float* src, in
   return source_rowmin_filtered_impl(tgt, src, nrows, Ns, Ns_pad, d, tol, scale_t, scale_s, 0, ws, rowmin, stream);
 }
 // the same with the bound pass on the hi halves only (one fp16 product per term instead of three: 1/3 of the matrix work); the
-// caller's tol must cover 2^-10 |x||y| per dot product on top of the accumulation error.  Needs scale_t, scale_s > 0 and
-// Ns_pad % 256 == 0, otherwise it runs the three-product pass.
+// caller's tol must cover 2^-10 |x||y| per dot product on top of the accumulation error.  Needs scale_t, scale_s > 0 (and
+// Ns_pad % 128 == 0 like every path: source_bound_dma_kernel skips the empty half of a last 256-source tile, pinned by the half_tile case
+// of tests/test_gpu_source_bound.py), otherwise it runs the three-product pass.
 extern "C" int ssg_source_rowmin_filtered1(const float* tgt, const float* src, int nrows, int Ns, int Ns_pad, int d, float tol, float scale_t, float scale_s,
                                            float* ws, uint32_t* rowmin, hipStream_t stream) {
   return source_rowmin_filtered_impl(tgt, src, nrows, Ns, Ns_pad, d, tol, scale_t, scale_s, 1, ws, rowmin, stream);

@@ -194,6 +194,42 @@ def range_stats(tgt, src=None):
     return rs.tolist()
 
 
+def source_bound_params(stats, d, bound, nrows, Ns_pad):
+    """(tol, scale_t, scale_s, workspace floats) of ssg_source_rowmin_filtered* -- the contract between the caller and the bound pass, on
+    the host alone.  stats = (max|tgt|, max|src|, max target row norm, max source row norm), upper bounds; bound = "half" (one fp16
+    product on the hi halves, ssg_source_rowmin_filtered1), "split" (three products on split-half operands) or anything else, e.g. "f32"
+    (float32 MFMA, scales 0).  Every bound the pass writes is within tol / 2 of the true minimum of its granule: tol is two per-distance
+    errors plus slack, so a granule more than tol above the row's smallest bound cannot hold the row's minimum."""
+    import math
+    # rigorous float32 error bound of |x|^2 + |y|^2 - 2<x,y>: the MFMA dot is a d-term fmaf chain
+    # (|err| <= gamma_d * sum|x_k y_k| <= gamma_d |x||y|, gamma_d = d*u/(1-d*u), u = 2^-24); the squared
+    # norms come from a 32-term chain + 6-level tree (38 u relative); a few ulps for the final adds.
+    mt, ms, nx, ny = (float(s) for s in stats)
+    u = 2.0 ** -24
+    split = bound in ("split", "half")
+    one = bound == "half"        # bound pass on the hi halves only (plain fp16 GEMM); "split" = three products (fp32-class)
+    st = ss = 0.0
+    if split:
+        # bound pass on the fp16 matrix cores (split-half operands): per product 3*2^-22 relative (two operand
+        # representations + the dropped lo*lo term) + 2^-24 absolute per operand below the half normals; the
+        # accumulation is at most a 3d-term chain (three MFMA products per term), whatever order the hardware adds in
+        st = 256.0 if mt == 0 else min(256.0, 2.0 ** math.floor(math.log2(16384.0 / mt)))
+        ss = 256.0 if ms == 0 else min(256.0, 2.0 ** math.floor(math.log2(16384.0 / ms)))
+        gam = 3.0 * d * u * 1.01 / (1.0 - 3.0 * d * u)
+        dot_err = (gam + 12.0 * u) * nx * ny + u * math.sqrt(d) * (nx / ss + ny / st) * 1.01
+        if one:
+            # hi halves only: each operand carries a relative error 2^-11 (+ 2^-25 absolute below the half normals, covered
+            # by the second term above), so |x.y - xh.yh| <= (2^-10 + 2^-22) sum|x_k y_k| <= 2^-10 * 1.001 |x||y|; the
+            # accumulation is a d-term float32 chain (covered by gam)
+            dot_err += (2.0 ** -10) * 1.001 * nx * ny
+    else:
+        gam = d * u / (1.0 - d * u)
+        dot_err = gam * nx * ny
+    tol = 2.0 * (2.0 * dot_err + 40.0 * u * (nx * nx + ny * ny)) + 8.0 * u * (nx + ny) ** 2
+    nws = nrows + Ns_pad + nrows * (Ns_pad // 8) + ((nrows + Ns_pad) * d if split else 0)
+    return tol, st, ss, nws
+
+
 def source_vector(src, tgt, row0=0, nrows=None, exact_gemm=None, stats=None):
     """reid/rerank.py:35-40 on device -> (rowmin uint32-as-int32 [nrows]) for a row block.
 
@@ -215,36 +251,12 @@ def source_vector(src, tgt, row0=0, nrows=None, exact_gemm=None, stats=None):
     if not exact_gemm and (nrows * d * 4) < 2 ** 31:
         npad = (-Ns) % 256
         srcp = torch.nn.functional.pad(src, (0, 0, 0, npad)) if npad else src
-        # rigorous float32 error bound of |x|^2 + |y|^2 - 2<x,y>: the MFMA dot is a d-term fmaf chain
-        # (|err| <= gamma_d * sum|x_k y_k| <= gamma_d |x||y|, gamma_d = d*u/(1-d*u), u = 2^-24); the squared
-        # norms come from a 32-term chain + 6-level tree (38 u relative); a few ulps for the final adds.
         if stats is None:      # (max|tgt|, max|src|, max row norm of the block, max row norm of src): one host read
             stats = range_stats(tblk.contiguous(), src)
-        mt, ms, nx, ny = (float(s) for s in stats)
-        u = 2.0 ** -24
         bound = os.environ.get("SSG_SOURCE_BOUND", "half")
+        tol, st, ss, nws = source_bound_params(stats, d, bound, nrows, Ns + npad)
         split = bound in ("split", "half")
         one = bound == "half"        # bound pass on the hi halves only (plain fp16 GEMM); "split" = three products (fp32-class)
-        st = ss = 0.0
-        if split:
-            # bound pass on the fp16 matrix cores (split-half operands): per product 3*2^-22 relative (two operand
-            # representations + the dropped lo*lo term) + 2^-24 absolute per operand below the half normals; the
-            # accumulation is at most a 3d-term chain (three MFMA products per term), whatever order the hardware adds in
-            import math
-            st = 256.0 if mt == 0 else min(256.0, 2.0 ** math.floor(math.log2(16384.0 / mt)))
-            ss = 256.0 if ms == 0 else min(256.0, 2.0 ** math.floor(math.log2(16384.0 / ms)))
-            gam = 3.0 * d * u * 1.01 / (1.0 - 3.0 * d * u)
-            dot_err = (gam + 12.0 * u) * nx * ny + u * math.sqrt(d) * (nx / ss + ny / st) * 1.01
-            if one:
-                # hi halves only: each operand carries a relative error 2^-11 (+ 2^-25 absolute below the half normals, covered
-                # by the second term above), so |x.y - xh.yh| <= (2^-10 + 2^-22) sum|x_k y_k| <= 2^-10 * 1.001 |x||y|; the
-                # accumulation is a d-term float32 chain (covered by gam)
-                dot_err += (2.0 ** -10) * 1.001 * nx * ny
-        else:
-            gam = d * u / (1.0 - d * u)
-            dot_err = gam * nx * ny
-        tol = 2.0 * (2.0 * dot_err + 40.0 * u * (nx * nx + ny * ny)) + 8.0 * u * (nx + ny) ** 2
-        nws = nrows + Ns + npad + nrows * ((Ns + npad) // 8) + ((nrows + Ns + npad) * d if split else 0)
         ws = torch.empty(nws, dtype=torch.float32, device=tgt.device)
         fn = L.ssg_source_rowmin_filtered1 if (split and one) else L.ssg_source_rowmin_filtered
         check(fn(ptr(tblk), ptr(srcp), nrows, Ns, Ns + npad, d, tol, st, ss, ptr(ws), ptr(rowmin), stream()), "ssg_source_rowmin_filtered")
