@@ -61,30 +61,28 @@ __device__ __forceinline__ float4 split_decode4(const uint2 hi, const uint2 lo) 
 }
 
 struct ConvParams {
-  const float* in; const float* w; const float* bias; const float* res; float* out;
+  // (optional fields carry their default: a caller sets what differs)
+  const float* in; const float* w; const float* bias; const float* res = nullptr; float* out;
   int B, H, W, Cin, OH, OW, Cout, KH, KW, stride, pad, relu;
   int M, Kpad;   // M = B*OH*OW, Kpad = weight row length (multiple of 32)
-  int variant;   // tuning knob (SSG_CONV_VARIANT), 0 = default
   unsigned in_bytes;   // size of the input tensor (buffer-resource bound)
-  // optional second 1x1 input concatenated along K (fused downsample branch): k-tiles >= nk1 read in2
-  const float* in2; int H2, W2, Cin2, stride2, nk1; unsigned in2_bytes;
-  // epilogue mode 1 (pairwise distance, reid/evaluators.py:63-85): out = rowterm[m] + bias[col] - 2*acc
-  const float* rowterm; int epi;
+  // optional second 1x1 input concatenated along K (fused downsample branch): k-tiles >= nk1 read in2.  Without one nk1 = Kpad / 16 (every
+  // k-tile of either BK reads `in`); with one nk1 = Cin / 32 (it counts 32-wide tiles)
+  const float* in2 = nullptr; int H2 = 0, W2 = 0, Cin2 = 0, stride2 = 1, nk1; unsigned in2_bytes = 0;
+  // epilogue mode 1 (pairwise distance, reid/evaluators.py:63-85): out = rowterm[m] + bias[col] - 2*acc; mode 2 (cosine): out = 2 - 2*acc
+  const float* rowterm = nullptr; int epi = 0;
   // epilogue mode 3 (distance filter): no matrix store; per output row the minimum of rowterm+bias-2*acc over each
   // 8-column granule goes to tilemin[m * tmin_ld + column / 8]
-  float* tilemin; int tmin_ld;
-  // split-half format (see "split-half activations" below): which tensors are encoded, and the factor
+  float* tilemin = nullptr; int tmin_ld = 0;
+  // split-half format (see "split-half activations" above): which tensors are encoded, and the factor
   // that undoes the operand scaling (weights / features are pre-scaled by a power of two)
-  int out_split, res_split; float acc_scale;
+  int out_split = 0, res_split = 0; float acc_scale = 1.f;
   // per-output-channel factor applied to the accumulator before the bias (nullptr = none): the split-half path pre-scales
   // every weight ROW by its own power of two (folded checkpoints have per-channel BN scales spanning orders of magnitude)
   const float* cscale = nullptr;
   // set to 1 when a value that does not fit the split-half output format (|v| >= 65520 or NaN) is encoded (nullptr = no check)
   int* overflow = nullptr;
-  // 1 = only the hi x hi product of the split-half operands (a plain fp16 GEMM: 1/3 of the matrix work, error 2^-10 |x||y|;
-  // used by the source-term bound pass, whose tolerance covers it); 3 = the fp32-class three-product form
-  int products = 3;
-  // conv_dma_kernel, three-product instances: the same weights in the k-tile-major layout ssg_conv_weights_tile writes (nullptr = read `w`)
+  // conv_dma_kernel: the same weights in the k-tile-major layout ssg_conv_weights_tile writes (nullptr = read `w`)
   const float* wt = nullptr;
   unsigned long long* prof = nullptr;   // SSG_DMA_PROF builds (tools/micro/conv_prof.hip): 8 s_memtime stamps per workgroup of conv_dma_kernel
 };
@@ -330,12 +328,6 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64, (BM / WM) * (BN / WN) =
 
   const int nk = p.Kpad / CBK;
   const int l32 = lane & 31, h = lane >> 5;
-  // co-resident workgroups start in lockstep and would hit their non-MFMA phases together;
-  // distinct static priorities de-phase them so one wave's MFMAs cover the other's staging.
-  if (p.variant & 1) {
-    const int pr = ((int)blockIdx.x >> 8) & 3;
-    if (pr == 1) __builtin_amdgcn_s_setprio(1); else if (pr == 2) __builtin_amdgcn_s_setprio(2); else if (pr == 3) __builtin_amdgcn_s_setprio(3);
-  }
   // Branch-free pipeline: the tile index of a prefetch is clamped to the last tile (a harmless reload) and the
   // stage write after the last tile is redundant, so no load or register definition sits under a condition
   // (hipcc otherwise waits for the loads at the join).
@@ -414,7 +406,7 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64, (BM / WM) * (BN / WN) =
   }
   const float* __restrict__ resp = p.res;
   float* __restrict__ outp = p.out;
-  if (p.epi == 0 && !(p.variant & 2)) {
+  if (p.epi == 0) {
     // Convolution epilogue, coalesced: the accumulators have one PIXEL per lane (row stride Cout*4 bytes), so direct
     // stores touch 64 cache lines per instruction.  Each wave instead turns its tile through a private LDS patch, 32
     // pixels x WN channels at a time, and leaves with lanes running along the channels: every residual load / output
@@ -559,27 +551,18 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64, (BM / WM) * (BN / WN) =
 // 16 waves: a third fewer global -> LDS bytes per MFMA than 128 x 256, which is what bounds these kernels).
 // DUAL: a second 1x1 input is concatenated along K (fused downsample branch); a compile-time switch, because the main loop is bound
 // by instruction issue (every branch, scalar division and v_readfirstlane per k-tile shows).
-// NS: LDS stages (NS - 1 k-tiles in flight).  The 1x1 convolutions that stream their pixel operand from HBM (K = 512 ... 2048) sat at
-// 0.4 of the matrix peak AND 0.4 of the HBM rate with two 32 KB tiles in flight per CU: bytes in flight / memory latency was the
-// bound (64 KB / ~3 us = 21 GB/s per CU).  The 256 x 256 kernel (one workgroup per CU, 96 of 160 KB of LDS) takes a fourth stage.
-// WM_ = 128 (256 x 256 tile only): 8 waves of 128 x 64 instead of 16 of 64 x 64 -- 12 fragment reads per 24 MFMAs instead of 8 per 12 (a
-// quarter fewer LDS bytes per MFMA), half the waves at every barrier, 2 waves per SIMD with up to 256 VGPRs each.  TWOSET: the fragments
-// of k-tile t + 1 are read into a second register set right after the barrier that publishes them, under the last MFMA group of tile t
-// (source_bound_dma_kernel's schedule).
+// Stages: three (two k-tiles in flight); the 256 x 256 kernel (one workgroup per CU, 128 of 160 KB of LDS) takes a fourth.  The 1x1 convolutions
+// that stream their pixel operand from HBM (K = 512 ... 2048) sat at 0.4 of the matrix peak AND 0.4 of the HBM rate with two 32 KB tiles in
+// flight per CU: bytes in flight / memory latency was the bound (64 KB / ~3 us = 21 GB/s per CU).
 // LINE: fetch order of the pixel operand.  0 = one k-tile (64 bytes per pixel row) per step; 1 = the two k-tiles of a 32-channel run, i.e. both
 // halves of a 128-byte line, requested back to back at every other step (same stages, same multiply order: bit-identical).  Needs an even
-// number of k-tiles and runs of 32 channels in both inputs -- the launchers check it (conv_line_order).
-#ifndef SSG_DMA_BPOS
-#define SSG_DMA_BPOS 2
-#endif
-template <int BN, bool ONEPROD = false, int BM = 128, bool DUAL = false, int NS = 3, int WM_ = 64, bool TWOSET = false, int LINE = 0>
-__global__ __launch_bounds__((BM / WM_) * (BN / 64) * 64, BM == 256 ? 1 : (BN == 256 ? 4 : 3)) void conv_dma_kernel(ConvParams p) {   // 4 (3) waves per SIMD: at most 128 (168) VGPRs
-  static_assert(NS == 3 || NS == 4, "three or four stages");
-  static_assert(WM_ == 64 || (WM_ == 128 && BM == 256 && BN == 256 && !ONEPROD && NS == 4), "128-row wave tiles: the 256 x 256 three-product kernel");
-  static_assert(!TWOSET || WM_ == 128, "second fragment set: 8-wave kernel only");
-  static_assert(LINE == 0 || (LINE == 1 && !ONEPROD && !TWOSET), "line order: three-product kernels with one fragment set");
-  constexpr int LN = SSG_DMA_BPOS > 0 ? LINE : 0;                   // (A/B builds with the barrier in front of the multiply keep the k-tile order)
-  constexpr int WM = WM_, WN = 64, MT = WM / 32, NT = 2, CBK = 16;
+// number of k-tiles and runs of 32 channels in both inputs -- conv_route checks it.
+template <int BM, int BN, bool DUAL = false, int LINE = 0>
+__global__ __launch_bounds__((BM / 64) * (BN / 64) * 64, BM == 256 ? 1 : (BN == 256 ? 4 : 3)) void conv_dma_kernel(ConvParams p) {   // 4 (3) waves per SIMD: at most 128 (168) VGPRs
+  static_assert((BM == 128 && (BN == 128 || BN == 256)) || (BM == 256 && BN == 256), "128 x 128, 128 x 256 or 256 x 256 tiles");
+  static_assert(LINE == 0 || LINE == 1, "k-tile order or line order");
+  constexpr int NS = BM == 256 ? 4 : 3;                             // LDS stages (NS - 1 k-tiles in flight)
+  constexpr int WM = 64, WN = 64, MT = WM / 32, NT = 2, CBK = 16;
   constexpr int WCOLS = BN / WN, NW = (BM / WM) * WCOLS;             // 8 waves (2 x 4) for 128 x 256, 4 waves (2 x 2) for 128 x 128, 16 (4 x 4) for 256 x 256
   constexpr int ABLK = BM / 16 / NW, WBLK = BN / 16 / NW;            // 16-row A / W blocks per wave and stage: 1 or 2
   constexpr int STAGE_BYTES = (BM + BN) * 64;                       // [A: BM rows x 64 B][W: BN rows x 64 B]
@@ -620,11 +603,8 @@ __global__ __launch_bounds__((BM / WM_) * (BN / 64) * 64, BM == 256 ? 1 : (BN ==
   // cache line per row).  Tiled `wt` (ssg_conv_weights_tile): [Cout / 128][Kpad / 16] granules of 128 rows x 64 bytes with the slot swizzle
   // already applied, i.e. the byte image of this stage part -- lane l reads base + 16 * l, 1 KB contiguous per instruction.  The choice is
   // wave-uniform and made here, once: the loop below adds the same two offsets either way (kb_ = dn << wkshift instead of dn << 6).
-#ifndef SSG_CONV_WT
-#define SSG_CONV_WT 1          /* 0: ignore ConvParams.wt (A/B builds: tools/ab_inproc.py interleaves the two libraries) */
-#endif
   const int nk = p.Kpad / CBK;
-  const bool tiled = SSG_CONV_WT && !ONEPROD && p.wt != nullptr;
+  const bool tiled = p.wt != nullptr;
   const __amdgpu_buffer_rsrc_t w_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(tiled ? p.wt : p.w), 0, (unsigned)((int64_t)p.Cout * p.Kpad * 4), 0x00020000);
   const int wrow0 = tn * BN + wave * (16 * WBLK);                  // first weight row of this wave's block(s): both lie in one 128-row granule
   const unsigned wo0 = tiled ? (unsigned)((((wrow0 >> 7) * nk) * 128 + (wrow0 & 127)) * 64 + lane * 16) : (unsigned)(((wrow0 + drow) * p.Kpad + lc4) * 4);
@@ -635,21 +615,15 @@ __global__ __launch_bounds__((BM / WM_) * (BN / 64) * 64, BM == 256 ? 1 : (BN ==
   // and a lane's address is its tap-(0,0) offset + one uniform delta (out-of-range taps: the offset is replaced, not clamped).
   int dn = 0, dr = 0, ds = 0, dch = 0;
   [[maybe_unused]] int dnw = 0;                                     // LINE = 1: the weight cursor (dn is then the even tile of the next pixel pair)
-#ifndef SSG_DMA_AUX_A
-#define SSG_DMA_AUX_A 0        /* cache policy of the activation DMA (2 = nt): A/B knob, measured neutral */
-#endif
-#ifndef SSG_DMA_AUX_W
-#define SSG_DMA_AUX_W 0
-#endif
 #define SSG_DMA_A(J, ST)                                                                                             \
   {                                                                                                                  \
     if (!DUAL || dn < nkA) {                                                                                          \
       const bool ok = ab##J >= 0 && (unsigned)(ah##J + dr) < (unsigned)p.H && (unsigned)(aw##J + ds) < (unsigned)p.W;  \
       const unsigned aoff = ok ? (unsigned)(abase##J + ddelta_) : 0x80000000u;                                        \
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(in_rsrc, SSG_LDSP(ST + (wave * ABLK + J) * 1024), 16, aoff, 0, 0, SSG_DMA_AUX_A);   \
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(in_rsrc, SSG_LDSP(ST + (wave * ABLK + J) * 1024), 16, aoff, 0, 0, 0);   \
     } else {                                                                                                          \
       const unsigned aoff = a2b##J + (unsigned)((dn - nkA) * CBK * 4);                                                 \
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(in2_rsrc, SSG_LDSP(ST + (wave * ABLK + J) * 1024), 16, aoff, 0, 0, SSG_DMA_AUX_A);  \
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(in2_rsrc, SSG_LDSP(ST + (wave * ABLK + J) * 1024), 16, aoff, 0, 0, 0);  \
     }                                                                                                                 \
   }
 #define SSG_DMA_NEXT(ST)                                                                                             \
@@ -657,8 +631,8 @@ __global__ __launch_bounds__((BM / WM_) * (BN / 64) * 64, BM == 256 ? 1 : (BN ==
     const int ddelta_ = ((dr * p.W + ds) * p.Cin + dch * 32 + (dn & 1) * 16) * 4;                                     \
     SSG_DMA_A(0, ST) if (ABLK == 2) SSG_DMA_A(1, ST)                                                                  \
     const unsigned kb_ = (unsigned)dn << wkshift;                                                                     \
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rsrc, SSG_LDSP(ST + BM * 64 + wave * (1024 * WBLK)), 16, wo0 + kb_, 0, 0, SSG_DMA_AUX_W);   \
-    if (WBLK == 2) __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rsrc, SSG_LDSP(ST + BM * 64 + wave * 2048 + 1024), 16, wo1 + kb_, 0, 0, SSG_DMA_AUX_W); \
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rsrc, SSG_LDSP(ST + BM * 64 + wave * (1024 * WBLK)), 16, wo0 + kb_, 0, 0, 0);   \
+    if (WBLK == 2) __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rsrc, SSG_LDSP(ST + BM * 64 + wave * 2048 + 1024), 16, wo1 + kb_, 0, 0, 0); \
     {                                        /* branch-free advance; the tail re-fetches the last tile (harmless, keeps the vmcnt accounting uniform) */ \
       const int adv_ = dn < nk - 1 ? 1 : 0;                                                                          \
       dn += adv_;                                                                                                    \
@@ -677,12 +651,12 @@ __global__ __launch_bounds__((BM / WM_) * (BN / 64) * 64, BM == 256 ? 1 : (BN ==
     if (!DUAL || dn < nkA) {                                                                                          \
       const bool ok = ab##J >= 0 && (unsigned)(ah##J + dr) < (unsigned)p.H && (unsigned)(aw##J + ds) < (unsigned)p.W;  \
       aoff = ok ? (unsigned)(abase##J + ddelta_) : 0x80000000u;                                                       \
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(in_rsrc, SSG_LDSP(STE + (wave * ABLK + J) * 1024), 16, aoff, 0, 0, SSG_DMA_AUX_A);        \
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(in_rsrc, SSG_LDSP(STO + (wave * ABLK + J) * 1024), 16, aoff + 64u, 0, 0, SSG_DMA_AUX_A);  \
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(in_rsrc, SSG_LDSP(STE + (wave * ABLK + J) * 1024), 16, aoff, 0, 0, 0);        \
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(in_rsrc, SSG_LDSP(STO + (wave * ABLK + J) * 1024), 16, aoff + 64u, 0, 0, 0);  \
     } else {                                                                                                          \
       aoff = a2b##J + (unsigned)((dn - nkA) * CBK * 4);                                                                \
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(in2_rsrc, SSG_LDSP(STE + (wave * ABLK + J) * 1024), 16, aoff, 0, 0, SSG_DMA_AUX_A);       \
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(in2_rsrc, SSG_LDSP(STO + (wave * ABLK + J) * 1024), 16, aoff + 64u, 0, 0, SSG_DMA_AUX_A); \
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(in2_rsrc, SSG_LDSP(STE + (wave * ABLK + J) * 1024), 16, aoff, 0, 0, 0);       \
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(in2_rsrc, SSG_LDSP(STO + (wave * ABLK + J) * 1024), 16, aoff + 64u, 0, 0, 0); \
     }                                                                                                                 \
   }
 #define SSG_DMA_PAIR(STE, STO)                                                                                       \
@@ -700,8 +674,8 @@ __global__ __launch_bounds__((BM / WM_) * (BN / 64) * 64, BM == 256 ? 1 : (BN ==
 #define SSG_DMA_W(ST)                                                                                                \
   {                                                                                                                  \
     const unsigned kb_ = (unsigned)dnw << wkshift;                                                                    \
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rsrc, SSG_LDSP(ST + BM * 64 + wave * (1024 * WBLK)), 16, wo0 + kb_, 0, 0, SSG_DMA_AUX_W);   \
-    if (WBLK == 2) __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rsrc, SSG_LDSP(ST + BM * 64 + wave * 2048 + 1024), 16, wo1 + kb_, 0, 0, SSG_DMA_AUX_W); \
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rsrc, SSG_LDSP(ST + BM * 64 + wave * (1024 * WBLK)), 16, wo0 + kb_, 0, 0, 0);   \
+    if (WBLK == 2) __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rsrc, SSG_LDSP(ST + BM * 64 + wave * 2048 + 1024), 16, wo1 + kb_, 0, 0, 0); \
     dnw += dnw < nk - 1 ? 1 : 0;                                                                                     \
   }
 
@@ -709,22 +683,6 @@ __global__ __launch_bounds__((BM / WM_) * (BN / 64) * 64, BM == 256 ? 1 : (BN ==
   const int g = (l32 >> 2) & 3;
   const int offh = ((2 * h) ^ g) * 16, offl = ((2 * h + 1) ^ g) * 16;
   const int arow = (wm * WM + l32) * 64, brow = BM * 64 + (wn * WN + l32) * 64;
-#define SSG_MMA(ST)                                                                                                  \
-  {                                                                                                                  \
-    v8h ah_[MT], al_[MT], bh_[NT], bl_[NT];                                                                          \
-    _Pragma("unroll") for (int i = 0; i < MT; i++) {                                                                 \
-      ah_[i] = *reinterpret_cast<const v8h*>(ST + arow + i * 2048 + offh); al_[i] = *reinterpret_cast<const v8h*>(ST + arow + i * 2048 + offl); } \
-    _Pragma("unroll") for (int j = 0; j < NT; j++) {                                                                 \
-      bh_[j] = *reinterpret_cast<const v8h*>(ST + brow + j * 2048 + offh); bl_[j] = *reinterpret_cast<const v8h*>(ST + brow + j * 2048 + offl); } \
-    if constexpr (!ONEPROD) {                                                                                        \
-      _Pragma("unroll") for (int i = 0; i < MT; i++) _Pragma("unroll") for (int j = 0; j < NT; j++)                  \
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh_[j], al_[i], acc[i][j], 0, 0, 0);                      \
-      _Pragma("unroll") for (int i = 0; i < MT; i++) _Pragma("unroll") for (int j = 0; j < NT; j++)                  \
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bl_[j], ah_[i], acc[i][j], 0, 0, 0);                      \
-    }                                                                                                                \
-    _Pragma("unroll") for (int i = 0; i < MT; i++) _Pragma("unroll") for (int j = 0; j < NT; j++)                    \
-      acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh_[j], ah_[i], acc[i][j], 0, 0, 0);                        \
-  }
 
   v16f acc[MT][NT];
 #pragma unroll
@@ -734,157 +692,47 @@ __global__ __launch_bounds__((BM / WM_) * (BN / 64) * 64, BM == 256 ? 1 : (BN ==
 #pragma unroll
       for (int r = 0; r < 16; r++) acc[i][j][r] = 0.f;
 
-  // Three stages, loads two K tiles ahead.  `__syncthreads()` would make hipcc wait for EVERY outstanding DMA (vmcnt(0)),
-  // i.e. for the tile it issued a moment ago; the explicit pair below waits only for the older tile (each tile is 3 or 4 DMA
-  // instructions per wave) and then publishes it.  The compiler's own tracking of the DMA -> LDS-array dependencies stays in
-  // force for the fragment reads (separate __shared__ arrays per stage).
-  // (NS stages: NS - 1 tiles in flight, the wait leaves the NS - 2 newest tiles' DMAs outstanding)
-  // lgkmcnt(0) belongs to the protocol: the barrier also tells the other waves "I am done READING the stage you overwrite next",
-  // and hipcc sinks the (register-only) MFMAs of the previous tile -- and with them the lgkmcnt waits for its fragment reads --
-  // below this asm statement.  Without the wait a wave passed the barrier with fragment reads still queued in the LDS pipeline,
-  // and under load another wave's DMA overwrote the stage first: a few wrong 16-byte chunks (hi or lo halves of a later k-tile) in
-  // about two output tiles per 1600 -- found in round 3 by the tile-shape equality test, present since the kernel was written.
-#define SSG_PUBLISH()                                                                                              \
-  { constexpr int OUTST = (ABLK + WBLK) * (NS - 2);                                                                \
-    if (OUTST == 8) asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)\n\ts_barrier" ::: "memory");                                  \
-    else if (OUTST == 6) asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)\n\ts_barrier" ::: "memory");                             \
-    else if (OUTST == 4) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)\n\ts_barrier" ::: "memory");                             \
-    else if (OUTST == 3) asm volatile("s_waitcnt vmcnt(3) lgkmcnt(0)\n\ts_barrier" ::: "memory");                             \
-    else asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-  static_assert((ABLK + WBLK) * (NS - 2) == 8 || (ABLK + WBLK) * (NS - 2) == 6 || (ABLK + WBLK) * (NS - 2) == 4 || (ABLK + WBLK) * (NS - 2) == 3 ||
-                (ABLK + WBLK) * (NS - 2) == 2, "vmcnt literal for this tile shape");
-  // BPOS > 0 (three-product kernels): the publishing barrier sits INSIDE a tile's multiply -- after its first (BPOS = 1) or second
-  // (BPOS = 2) group of four MFMAs, when the hardware has consumed every fragment of the tile anyway, so lgkmcnt(0) costs nothing and the
-  // remaining MFMAs of the tile are still queued behind the barrier: the matrix pipe has work while the next tile's fragment reads are
-  // in flight (with the barrier in front of the whole multiply every wave of the CU read LDS at the same time and the pipes drained).
-  // All NS stages are in flight ahead of the first tile; the DMA of tile t + NS goes into the stage of tile t right after the barrier.
-  constexpr int BPOS = ONEPROD ? 0 : SSG_DMA_BPOS;
+  // NS stages, all in flight ahead of the first tile: the loads run NS - 1 k-tiles ahead and the DMA of tile t + NS goes into the stage of
+  // tile t right after the barrier of step t.  `__syncthreads()` would make hipcc wait for EVERY outstanding DMA (vmcnt(0)), i.e. for the
+  // tile it issued a moment ago; the explicit `s_waitcnt vmcnt(n) lgkmcnt(0)` + `s_barrier` pair of a step waits only for the oldest tile in
+  // flight (each tile is TDMA = 2, 3 or 4 DMA instructions per wave) and then publishes it.  The compiler's own tracking of the DMA ->
+  // LDS-array dependencies stays in force for the fragment reads (separate __shared__ arrays per stage).
+  // The publishing barrier sits INSIDE a tile's multiply -- after its second group of four MFMAs, when the hardware has consumed every
+  // fragment of the tile anyway, so lgkmcnt(0) costs nothing and the remaining MFMAs of the tile are still queued behind the barrier: the
+  // matrix pipe has work while the next tile's fragment reads are in flight (with the barrier in front of the whole multiply every wave of
+  // the CU read LDS at the same time and the pipes drained).
   constexpr int TDMA = ABLK + WBLK;                                  // DMA instructions per wave and tile
   const int nfull = nk / NS * NS;
-  if constexpr (BPOS == 0) {
-  SSG_DMA_NEXT(st0)
-  SSG_DMA_NEXT(st1)
-  if constexpr (NS == 4) SSG_DMA_NEXT(st2)
-  for (int kt = 0; kt < nfull; kt += NS) {   // tile t lives in stage array t % NS; no exits inside (they doubled the accumulators)
-    if constexpr (NS == 3) {
-      SSG_PUBLISH();                        // tile kt landed in st0 for every wave; everybody is done reading st2 (tile kt-1)
-      SSG_DMA_NEXT(st2)
-      __builtin_amdgcn_sched_barrier(0);    // keep the DMA issue ahead of the multiply
-      SSG_MMA(st0)
-      SSG_PUBLISH();
-      SSG_DMA_NEXT(st0)
-      __builtin_amdgcn_sched_barrier(0);
-      SSG_MMA(st1)
-      SSG_PUBLISH();
-      SSG_DMA_NEXT(st1)
-      __builtin_amdgcn_sched_barrier(0);
-      SSG_MMA(st2)
-    } else {
-      SSG_PUBLISH();                        // tile kt landed in st0 for every wave; everybody is done reading st3 (tile kt-1)
-      SSG_DMA_NEXT(st3)
-      __builtin_amdgcn_sched_barrier(0);
-      SSG_MMA(st0)
-      SSG_PUBLISH();
-      SSG_DMA_NEXT(st0)
-      __builtin_amdgcn_sched_barrier(0);
-      SSG_MMA(st1)
-      SSG_PUBLISH();
-      SSG_DMA_NEXT(st1)
-      __builtin_amdgcn_sched_barrier(0);
-      SSG_MMA(st2)
-      SSG_PUBLISH();
-      SSG_DMA_NEXT(st2)
-      __builtin_amdgcn_sched_barrier(0);
-      SSG_MMA(st3)
-    }
-  }
-  if (nk - nfull >= 1) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory"); SSG_MMA(st0) }
-  if (nk - nfull >= 2) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory"); SSG_MMA(st1) }
-  if constexpr (NS == 4) { if (nk - nfull == 3) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory"); SSG_MMA(st2) } }
-  } else if constexpr (TWOSET) {
-    v8h fah[2][MT], fal[2][MT], fbh[2][NT], fbl[2][NT];     // [register set][tile]
-#define SSG_READS2(ST, S)                                                                                            \
-    { _Pragma("unroll") for (int i = 0; i < MT; i++) {                                                               \
-        fah[S][i] = *reinterpret_cast<const v8h*>(ST + arow + i * 2048 + offh); fal[S][i] = *reinterpret_cast<const v8h*>(ST + arow + i * 2048 + offl); } \
-      _Pragma("unroll") for (int j = 0; j < NT; j++) {                                                               \
-        fbh[S][j] = *reinterpret_cast<const v8h*>(ST + brow + j * 2048 + offh); fbl[S][j] = *reinterpret_cast<const v8h*>(ST + brow + j * 2048 + offl); } }
-#define SSG_GA(S) { _Pragma("unroll") for (int i = 0; i < MT; i++) _Pragma("unroll") for (int j = 0; j < NT; j++)   \
-      acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fbh[S][j], fal[S][i], acc[i][j], 0, 0, 0); }
-#define SSG_GB(S) { _Pragma("unroll") for (int i = 0; i < MT; i++) _Pragma("unroll") for (int j = 0; j < NT; j++)   \
-      acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fbl[S][j], fah[S][i], acc[i][j], 0, 0, 0); }
-#define SSG_GC(S) { _Pragma("unroll") for (int i = 0; i < MT; i++) _Pragma("unroll") for (int j = 0; j < NT; j++)   \
-      acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fbh[S][j], fah[S][i], acc[i][j], 0, 0, 0); }
-    // k-tile t (fragments in set S): the first two MFMA groups, publish tile t + 1 (and: everybody is done reading this stage -- its
-    // fragment reads were waited for one step ago), refill this stage with tile t + NS, read tile t + 1's fragments into the other set,
-    // the third group
-#define SSG_STEP2(ST, STN, S)                                                                                        \
-    { SSG_GA(S) SSG_GB(S)                                                                                            \
-      __builtin_amdgcn_sched_barrier(0);                                                                             \
-      asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(TDMA * (NS - 2)) : "memory");                  \
-      SSG_DMA_NEXT(ST)                                                                                               \
-      SSG_READS2(STN, 1 - (S))                                                                                       \
-      __builtin_amdgcn_sched_barrier(0);                                                                             \
-      SSG_GC(S) }
-    SSG_DMA_NEXT(st0)
-    SSG_DMA_NEXT(st1)
-    SSG_DMA_NEXT(st2)
-    SSG_DMA_NEXT(st3)
-    asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(TDMA * (NS - 1)) : "memory");     // tile 0 landed for everybody
-    SSG_READS2(st0, 0)
-    for (int kt = 0; kt < nfull; kt += NS) {
-      SSG_STEP2(st0, st1, 0)
-      SSG_STEP2(st1, st2, 1)
-      SSG_STEP2(st2, st3, 0)
-      SSG_STEP2(st3, st0, 1)
-    }
-    // left-over tiles (nk % NS): set 0 holds the fragments of tile nfull (published by the last barrier of the loop, or by the one above)
-    if (nk - nfull >= 1) { SSG_GA(0) SSG_GB(0) SSG_GC(0) }
-    if (nk - nfull >= 2) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory"); SSG_READS2(st1, 0) SSG_GA(0) SSG_GB(0) SSG_GC(0) }
-    if (nk - nfull == 3) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory"); SSG_READS2(st2, 0) SSG_GA(0) SSG_GB(0) SSG_GC(0) }
-#undef SSG_STEP2
-#undef SSG_GA
-#undef SSG_GB
-#undef SSG_GC
-#undef SSG_READS2
-  } else {
-    v8h fah[MT], fal[MT], fbh[NT], fbl[NT];
+  v8h fah[MT], fal[MT], fbh[NT], fbl[NT];
 #define SSG_READS(ST)                                                                                                \
-    { _Pragma("unroll") for (int i = 0; i < MT; i++) {                                                               \
-        fah[i] = *reinterpret_cast<const v8h*>(ST + arow + i * 2048 + offh); fal[i] = *reinterpret_cast<const v8h*>(ST + arow + i * 2048 + offl); } \
-      _Pragma("unroll") for (int j = 0; j < NT; j++) {                                                               \
-        fbh[j] = *reinterpret_cast<const v8h*>(ST + brow + j * 2048 + offh); fbl[j] = *reinterpret_cast<const v8h*>(ST + brow + j * 2048 + offl); } }
+  { _Pragma("unroll") for (int i = 0; i < MT; i++) {                                                               \
+      fah[i] = *reinterpret_cast<const v8h*>(ST + arow + i * 2048 + offh); fal[i] = *reinterpret_cast<const v8h*>(ST + arow + i * 2048 + offl); } \
+    _Pragma("unroll") for (int j = 0; j < NT; j++) {                                                               \
+      fbh[j] = *reinterpret_cast<const v8h*>(ST + brow + j * 2048 + offh); fbl[j] = *reinterpret_cast<const v8h*>(ST + brow + j * 2048 + offl); } }
 #define SSG_G1 { _Pragma("unroll") for (int i = 0; i < MT; i++) _Pragma("unroll") for (int j = 0; j < NT; j++)      \
-      acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fbh[j], fal[i], acc[i][j], 0, 0, 0); }
+    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fbh[j], fal[i], acc[i][j], 0, 0, 0); }
 #define SSG_G2 { _Pragma("unroll") for (int i = 0; i < MT; i++) _Pragma("unroll") for (int j = 0; j < NT; j++)      \
-      acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fbl[j], fah[i], acc[i][j], 0, 0, 0); }
+    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fbl[j], fah[i], acc[i][j], 0, 0, 0); }
 #define SSG_G3 { _Pragma("unroll") for (int i = 0; i < MT; i++) _Pragma("unroll") for (int j = 0; j < NT; j++)      \
-      acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fbh[j], fah[i], acc[i][j], 0, 0, 0); }
-    // one tile: fragments, the first MFMA groups, publish (tile t + 1 landed for everybody, everybody done reading this stage),
-    // refill this stage with tile t + NS, the rest of the multiply
-#ifndef SSG_DMA_SETPRIO
-#define SSG_DMA_SETPRIO 0      /* 1: s_setprio 1 around the MFMA groups (round 6 A/B, MI355X guide T5) */
-#endif
-#if SSG_DMA_SETPRIO
-#define SSG_PRIO(P_) __builtin_amdgcn_s_setprio(P_);
-#else
-#define SSG_PRIO(P_)
-#endif
-#define SSG_STEP(ST)                                                                                                 \
-    { SSG_READS(ST)                                                                                                  \
-      SSG_PRIO(1)                                                                                                    \
-      SSG_G1                                                                                                         \
-      if constexpr (BPOS == 2) SSG_G2                                                                                \
-      SSG_PRIO(0)                                                                                                    \
-      __builtin_amdgcn_sched_barrier(0);                                                                             \
-      asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(TDMA * (NS - 2)) : "memory");                  \
-      SSG_DMA_NEXT(ST)                                                                                               \
-      __builtin_amdgcn_sched_barrier(0);                                                                             \
-      SSG_PRIO(1)                                                                                                    \
-      if constexpr (BPOS == 1) SSG_G2                                                                                \
-      SSG_G3                                                                                                         \
-      SSG_PRIO(0) }
+    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fbh[j], fah[i], acc[i][j], 0, 0, 0); }
+  // one tile: fragments, the first MFMA groups, publish (tile t + 1 landed for everybody, everybody done reading this stage),
+  // refill this stage with tile t + NS, the rest of the multiply.
+  // lgkmcnt(0) belongs to the protocol: the barrier also tells the other waves "I am done READING the stage you overwrite next", and hipcc
+  // sinks the (register-only) MFMAs -- and with them the lgkmcnt waits for their fragment reads -- below this asm statement.  Without the wait
+  // a wave passed the barrier with fragment reads still queued in the LDS pipeline, and under load another wave's DMA overwrote the stage
+  // first: a few wrong 16-byte chunks (hi or lo halves of a later k-tile) in about two output tiles per 1600 -- found in round 3 by the
+  // tile-shape equality test, present since the kernel was written.
+#define SSG_STEP(ST)                                                                                               \
+  { SSG_READS(ST)                                                                                                  \
+    SSG_G1                                                                                                         \
+    SSG_G2                                                                                                         \
+    __builtin_amdgcn_sched_barrier(0);                                                                             \
+    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(TDMA * (NS - 2)) : "memory");                  \
+    SSG_DMA_NEXT(ST)                                                                                               \
+    __builtin_amdgcn_sched_barrier(0);                                                                             \
+    SSG_G3 }
 #define SSG_LAST(ST) { SSG_READS(ST) SSG_G1 SSG_G2 SSG_G3 }
-    if constexpr (LN == 1) {
+  if constexpr (LINE == 1) {
     // Line order.  Step t multiplies tile t out of stage t % NS (ST), publishes tile t + 1 and then issues the weights of tile t + NS into ST
     // and, at every other step (PAIR: t odd for NS = 4, t even for NS = 3, so that t + NS - 1 is even), the pixel pieces of tiles t + NS - 1
     // and t + NS into the previous stage STP (free since step t - 1) and ST.  The even tile of a pair is requested NS - 2 steps before it is
@@ -901,13 +749,12 @@ __global__ __launch_bounds__((BM / WM_) * (BN / 64) * 64, BM == 256 ? 1 : (BN ==
 #define SSG_LSTEP(STP, ST, PAIR)                                                                                     \
     { SSG_READS(ST)                                                                                                  \
       SSG_G1                                                                                                         \
-      if constexpr (BPOS == 2) SSG_G2                                                                                \
+      SSG_G2                                                                                                         \
       __builtin_amdgcn_sched_barrier(0);                                                                             \
       asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"((PAIR) ? VM_PAIR : VM_NONE) : "memory");       \
       if constexpr ((PAIR) != 0) SSG_DMA_PAIR(STP, ST)                                                               \
       SSG_DMA_W(ST)                                                                                                  \
       __builtin_amdgcn_sched_barrier(0);                                                                             \
-      if constexpr (BPOS == 1) SSG_G2                                                                                \
       SSG_G3 }
     if constexpr (NS == 4) {
       SSG_DMA_W(st0)
@@ -929,7 +776,7 @@ __global__ __launch_bounds__((BM / WM_) * (BN / 64) * 64, BM == 256 ? 1 : (BN ==
       if (nk - kt >= 4) { SSG_LSTEP(st1, st2, 1) SSG_LSTEP(st2, st0, 0) }
     }
 #undef SSG_LSTEP
-    } else {
+  } else {
     SSG_DMA_NEXT(st0)
     SSG_DMA_NEXT(st1)
     SSG_DMA_NEXT(st2)
@@ -947,24 +794,21 @@ __global__ __launch_bounds__((BM / WM_) * (BN / 64) * 64, BM == 256 ? 1 : (BN ==
     if (nk - nfull >= 1) SSG_LAST(st0)
     if (nk - nfull >= 2) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory"); SSG_LAST(st1) }
     if constexpr (NS == 4) { if (nk - nfull == 3) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory"); SSG_LAST(st2) } }
-    }
+  }
 #undef SSG_READS
 #undef SSG_G1
 #undef SSG_G2
 #undef SSG_G3
 #undef SSG_STEP
 #undef SSG_LAST
-  }
   SSG_DMA_STAMP(2)
   __syncthreads();                        // drains the (clamped, redundant) tail DMAs before the stages become epilogue patches
   SSG_DMA_STAMP(3)
-#undef SSG_PUBLISH
 #undef SSG_DMA_NEXT
 #undef SSG_DMA_A
 #undef SSG_DMA_PAIR
 #undef SSG_DMA_A2
 #undef SSG_DMA_W
-#undef SSG_MMA
 #pragma unroll
   for (int i = 0; i < MT; i++)
 #pragma unroll
@@ -1003,9 +847,6 @@ __global__ __launch_bounds__((BM / WM_) * (BN / 64) * 64, BM == 256 ? 1 : (BN ==
   const int chunk = lane % CPR, prow = lane / CPR, odd = lane & 1;
   const float* __restrict__ resp = p.res;
   float* __restrict__ outp = p.out;
-#ifndef SSG_DMA_FAST_EPI
-#define SSG_DMA_FAST_EPI 1
-#endif
   // cache-policy bits (gfx950: 1 = sc0, 2 = nt, 16 = sc1) of the straight-line epilogue's residual loads / output stores, with and without a residual.
   // A conv3 + residual launch streams its residual (last use) and its 0.5 GB output once: with `nt` they take no line of the L2 that the pixel
   // tile of its four column tiles and the weights go through (layer3: 0.326 -> 0.306 ms, layer4: 0.231 -> 0.219; profiles/r06_ab_nt_policy.txt).  Stores of the
@@ -1027,7 +868,7 @@ __global__ __launch_bounds__((BM / WM_) * (BN / 64) * 64, BM == 256 ? 1 : (BN ==
   // requested BEFORE patch n is turned through LDS (two patches = 8 KB per wave in flight), the lane-pair exchanges are selects instead of
   // divergent branches, and the range flag is OR-accumulated and tested once.  Same operations on the same values in the same order:
   // bit-identical output (tests/test_gpu_parity.py::test_conv_fast_epilogue_matches_the_general_one).
-  if (SSG_DMA_FAST_EPI && p.variant != 7 && p.out_split && p.relu && p.cscale != nullptr && (resp == nullptr || p.res_split) &&
+  if (p.out_split && p.relu && p.cscale != nullptr && (resp == nullptr || p.res_split) &&
       ((int64_t)p.M + BM) * p.Cout * 4 < (int64_t)0xffffffff) {      // (+ BM: the byte offsets of the rows behind M in the last tile must not wrap)
     constexpr int NP = MT * NT;
     unsigned ovf = 0u;
@@ -1315,116 +1156,117 @@ static int launch_conv_bk(const ConvParams& p, hipStream_t stream) {
   hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WM, WN, CIN4, CBK, SPLIT>), dim3(tiles), dim3((BM / WM) * (BN / WN) * 64), lds, stream, p);
   return ssg_check_hip(hipGetLastError(), "conv_igemm_kernel");
 }
-// Fetch order of conv_dma_kernel's pixel operand (its template parameter LINE) for one launch.  The line order needs an even number of
-// k-tiles and 32-channel runs in both inputs (every shape the two convolution entry points accept has them; the distance GEMMs of the
-// source term come with any multiple of 16 and keep the k-tile order, as does the one-product bound pass).  SSG_CONV_LINE=0 / 1 forces the
-// order for every launch that can take it; unset, each instance runs the order that measured faster.
-enum ConvDmaInst { DMA_128 = 0, DMA_WIDE, DMA_WIDE_DUAL, DMA_TALL, DMA_TALL_DUAL };
-static int conv_line_order(const ConvParams& p, ConvDmaInst inst) {
-  static int knob = -2;
-  if (knob == -2) { const char* e = getenv("SSG_CONV_LINE"); knob = e ? (atoi(e) == 1 ? 1 : 0) : -1; }
-  if (p.products != 3 || p.epi != 0 || ((p.Kpad / 16) & 1) || (p.Cin % 32) || (p.in2 && (p.Cin2 % 32))) return 0;
-  if (knob >= 0) return knob;
-  // forward of 1000 images, both orders interleaved in one process (profiles/r08_ab_conv_line_fetch.txt): 128 x 128 - 3 / - 6 %, 128 x 256
-  // with a residual - 3 %, DUAL 0 ... - 2 %, 256 x 256 1x1 0 ... - 4 % and 3x3 - 5 %; the 256 x 256 DUAL instance (behind SSG_CONV_TALL_DUAL)
-  // was not timed and keeps the k-tile order
-  static const int dflt[5] = {1, 1, 1, 1, 0};
-  return dflt[inst];
-}
 
-// BK=16 stages (default): half the LDS of BK=32 -> 3 instead of 2 co-resident workgroups per CU, so one
-// workgroup's prologue / epilogue overlaps the others' MFMA phases.  The fused dual-input GEMM stays
-// on BK=32.  SSG_CONV_BK16_MAXK=<K> restricts BK=16 to reductions of at most K (tuning knob).
-template <int BM, int BN, int WM, int WN, bool CIN4>
-static int launch_conv(const ConvParams& p, hipStream_t stream, bool split = false) {
-  static int bk16_max = -1;   // measured on MI355X: BK=16 wins for every ResNet-50 layer (9.1k -> 9.8k img/s)
-  if (bk16_max < 0) { const char* e = getenv("SSG_CONV_BK16_MAXK"); bk16_max = e ? atoi(e) : 0x7fffffff; }
-  if (split) {
-    if constexpr (CIN4) return launch_conv_bk<BM, BN, WM, WN, true, 16, true>(p, stream);   // one k-step = 4 taps
-    else {
-      static int sbk16 = -1;   // SSG_SPLIT_BK16=<K>: reductions of at most K use BK=16 stages
-      if (sbk16 < 0) { const char* e = getenv("SSG_SPLIT_BK16"); sbk16 = e ? atoi(e) : 0; }     // round 6: 0 (was 256) -- short reductions take the LDS-DMA kernel below too
-      if (!p.in2 && p.Kpad <= sbk16) return launch_conv_bk<BM, BN, WM, WN, false, 16, true>(p, stream);
-      if constexpr (BM == 128 && BN == 128) {   // long reductions on 128x128 tiles: LDS-DMA kernel (SSG_CONV_DMA bit 1)
-        static int dma = -1;
-        // bit 1: round 2 measured it neutral (21.42 vs 21.46 k img/s); with the round-6 epilogue the layer2 entry launches gain (256 -> 128 1x1:
-        // 0.723 -> 0.653 ms, 128 -> 128 3x3 stride 2: 0.591 -> 0.523 ms per 1000 images; bit-identical, profiles/r06_ab_nt_policy.txt): on by default
-        if (dma < 0) { const char* e = getenv("SSG_CONV_DMA"); dma = e ? atoi(e) : 3; }
-        if ((dma & 2) && p.epi == 0 && !p.in2) {
-          const int tiles = ((p.M + 127) / 128) * (p.Cout / 128);
-          if (conv_line_order(p, DMA_128)) hipLaunchKernelGGL((conv_dma_kernel<128, false, 128, false, 3, 64, false, 1>), dim3(tiles), dim3(256), 0, stream, p);
-          else hipLaunchKernelGGL(conv_dma_kernel<128>, dim3(tiles), dim3(256), 0, stream, p);
-          return ssg_check_hip(hipGetLastError(), "conv_dma_kernel<128>");
-        }
-      }
-      return launch_conv_bk<BM, BN, WM, WN, false, 32, true>(p, stream);
-    }
+// ---- routing: which kernel instance runs a launch.  The environment knobs are read once per process (conv_knobs below); conv_route is a
+// pure function of the launch parameters and the knobs (tests/test_conv_route.py runs its text on the host).
+struct ConvKnobs {
+  int dma = 3;              // SSG_CONV_DMA: the LDS-DMA kernel takes bit 0 = the 128x256 / 256x256, bit 1 = the 128x128 launches; 0 = register-staged kernels everywhere
+  int line = -1;            // SSG_CONV_LINE=0 / 1 forces the fetch order of every launch that can take it; unset (-1): per instance, see conv_route
+  int wide_mintiles = 256;  // SSG_SPLIT_WIDE_MINTILES: 128x256 tiles when at least that many exist (0 = never)
+  int bn64_maxtiles = 300;  // SSG_SPLIT_BN64_MAXTILES: 128x64 tiles below that many 128x128 tiles
+  int tall_mintiles = 200;  // SSG_CONV_TALL_MINTILES: 256x256 tiles when at least that many exist (0 = never)
+  int tall_res = 0;         // SSG_CONV_TALL_RES=1: 256x256 tiles also for convolutions with a residual epilogue (tuning knob)
+  int tall_dual = 0;        // SSG_CONV_TALL_DUAL=1: ... and for the fused conv3 | downsample GEMMs (tuning knob)
+};
+enum ConvFamily { CONV_IGEMM = 0, CONV_DMA = 1 };   // conv_igemm_kernel (register-staged) / conv_dma_kernel
+struct ConvRoute { int family, BM, BN, BK, dual, line; };
+
+static ConvRoute conv_route(const ConvParams& p, bool split, bool cin4, const ConvKnobs& k) {
+  const bool dual = p.in2 != nullptr;
+  const int rows128 = (p.M + 127) / 128;
+  ConvRoute r = {CONV_IGEMM, 128, 128, 32, dual ? 1 : 0, 0};
+  // Tile.  128x256 tiles (8 waves) read the pixel tile once for 256 output channels: 3/4 of the global->LDS bytes per flop of the 128x128
+  // tile, which is what bounds the split kernels; short reductions stay on more, smaller workgroups, which overlap better.  Few 128x128
+  // tiles (deep layers: M = B*8*4) leave one workgroup per CU with nothing to overlap its staging with; 128x64 tiles double the workgroup
+  // count.  The distance filter of the source term (epi 3, Cout % 128 == 0) takes the widest tile its padded source count allows.
+  bool wide, bn64;
+  if (p.epi == 3) { wide = split && p.Cout % 256 == 0; bn64 = false; }
+  else if (cin4 || !split) { wide = false; bn64 = p.Cout % 128 != 0; }
+  else {
+    wide = k.wide_mintiles > 0 && p.Cout % 256 == 0 && p.Kpad >= 128 && rows128 * (p.Cout / 256) >= k.wide_mintiles;
+    bn64 = p.Cout % 128 != 0 || rows128 * (p.Cout / 128) < k.bn64_maxtiles;
   }
-  if (!p.in2 && p.Kpad <= bk16_max) return launch_conv_bk<BM, BN, WM, WN, CIN4, 16, false>(p, stream);
-  return launch_conv_bk<BM, BN, WM, WN, CIN4, 32, false>(p, stream);
-}
-
-// Few 128x128 tiles (deep layers: M = B*8*4) leave one workgroup per CU with nothing to overlap its staging
-// with; 128x64 tiles double the workgroup count.  SSG_SPLIT_BN64_MAXTILES=<T>: use them below T tiles.
-// 128x256 tiles (8 waves) read the pixel tile once for 256 output channels: 3/4 of the global->LDS bytes per flop of
-// the 128x128 tile, which is what bounds the split kernels.  SSG_SPLIT_WIDE_MINTILES=<T>: use them when at least T
-// such tiles exist (0 = never).
-static bool conv_prefers_wide(const ConvParams& p, bool split) {
-  static int mintiles = -1;
-  if (mintiles < 0) { const char* e = getenv("SSG_SPLIT_WIDE_MINTILES"); mintiles = e ? atoi(e) : 256; }
-  if (!split || mintiles <= 0 || (p.Cout % 256) || p.Kpad < 128) return false;   // short reductions: more, smaller workgroups overlap better
-  return ((p.M + 127) / 128) * (p.Cout / 256) >= mintiles;
-}
-
-// the LDS-DMA kernel takes the convolution-epilogue 128x256 launches (SSG_CONV_DMA: bit 0 = 128x256, bit 1 = 128x128
-// launches; 0 = register-staged kernels everywhere)
-static int launch_conv_wide(const ConvParams& p, hipStream_t stream) {
-  static int dma = -1;
-  if (dma < 0) { const char* e = getenv("SSG_CONV_DMA"); dma = e ? atoi(e) : 3; }
-  if ((dma & 1) && (p.epi == 0 || p.epi == 3) && (int64_t)p.Cout * p.Kpad * 4 < 0x7fffffffLL) {   // (weights go through a 2 GiB buffer resource)
-    // 256 x 256 tiles (16 waves, one workgroup per CU): a third fewer global -> LDS bytes per MFMA; taken when they fill the chip
-    // (SSG_CONV_TALL_MINTILES = least number of such tiles, 0 = never)
-    static int tall = -1;
-    if (tall < 0) { const char* e = getenv("SSG_CONV_TALL_MINTILES"); tall = e ? atoi(e) : 200; }
+  if (wide) r.BN = 256; else if (bn64) r.BN = 64;
+  // Kernel family and BK.  BK=16 stages: half the LDS of BK=32 -> 3 instead of 2 co-resident workgroups per CU, so one workgroup's
+  // prologue / epilogue overlaps the others' MFMA phases (BK=16 wins for every ResNet-50 layer, 9.1k -> 9.8k img/s); the register-staged
+  // split kernel (two prefetch sets) and the dual-input GEMM stay on BK=32; the stem's split k-step is 4 taps = BK 16.
+  bool dma;
+  if (wide) {
+    dma = (k.dma & 1) && (p.epi == 0 || p.epi == 3) && (int64_t)p.Cout * p.Kpad * 4 < 0x7fffffffLL;   // (weights go through a 2 GiB buffer resource)
+    // 256 x 256 tiles (16 waves, one workgroup per CU): a third fewer global -> LDS bytes per MFMA; taken when they fill the chip.
+    // Measured: -2.5 % (3x3) / -6 % (1x1) on layer3 shapes; with a residual epilogue +3 %
     const int tiles_tall = ((p.M + 255) / 256) * (p.Cout / 256);
-    static int tall_dual = -1;               // SSG_CONV_TALL_DUAL=1: also for the fused conv3 | downsample GEMMs (tuning knob)
-    if (tall_dual < 0) { const char* e = getenv("SSG_CONV_TALL_DUAL"); tall_dual = e ? atoi(e) : 0; }
-    if (tall > 0 && p.products == 3 && p.epi == 0 && p.in2 && tall_dual && tiles_tall >= tall) {
-      if (conv_line_order(p, DMA_TALL_DUAL)) hipLaunchKernelGGL((conv_dma_kernel<256, false, 256, true, 4, 64, false, 1>), dim3(tiles_tall), dim3(1024), 0, stream, p);
-      else hipLaunchKernelGGL((conv_dma_kernel<256, false, 256, true, 4>), dim3(tiles_tall), dim3(1024), 0, stream, p);
-      return ssg_check_hip(hipGetLastError(), "conv_dma_kernel<256x256, dual>");
-    }
-    static int tall_res = -1;                // SSG_CONV_TALL_RES=1: also for convolutions with a residual epilogue (tuning knob)
-    if (tall_res < 0) { const char* e = getenv("SSG_CONV_TALL_RES"); tall_res = e ? atoi(e) : 0; }
-    if (tall > 0 && p.products == 3 && p.epi == 0 && (!p.res || tall_res) && !p.in2 && tiles_tall >= tall) {   // measured: -2.5 % (3x3) / -6 % (1x1) on layer3 shapes; with a residual epilogue +3 %
-      static int tall_ns = -1;               // SSG_CONV_TALL_STAGES=3: the three-stage pipeline of round 2 (tuning knob)
-      if (tall_ns < 0) { const char* e = getenv("SSG_CONV_TALL_STAGES"); tall_ns = e ? atoi(e) : 4; }
-      static int tall_wm = -1;               // SSG_CONV_TALL_WM=128: 8 waves of 128 x 64; =129: the same with a second fragment register set
-      if (tall_wm < 0) { const char* e = getenv("SSG_CONV_TALL_WM"); tall_wm = e ? atoi(e) : 64; }
-      if (tall_wm == 128) hipLaunchKernelGGL((conv_dma_kernel<256, false, 256, false, 4, 128, false>), dim3(tiles_tall), dim3(512), 0, stream, p);
-      else if (tall_wm == 129) hipLaunchKernelGGL((conv_dma_kernel<256, false, 256, false, 4, 128, true>), dim3(tiles_tall), dim3(512), 0, stream, p);
-      else if (tall_ns == 4 && conv_line_order(p, DMA_TALL)) hipLaunchKernelGGL((conv_dma_kernel<256, false, 256, false, 4, 64, false, 1>), dim3(tiles_tall), dim3(1024), 0, stream, p);
-      else if (tall_ns == 4) hipLaunchKernelGGL((conv_dma_kernel<256, false, 256, false, 4>), dim3(tiles_tall), dim3(1024), 0, stream, p);
-      else hipLaunchKernelGGL((conv_dma_kernel<256, false, 256, false>), dim3(tiles_tall), dim3(1024), 0, stream, p);
-      return ssg_check_hip(hipGetLastError(), "conv_dma_kernel<256x256>");
-    }
-    const int tiles = ((p.M + 127) / 128) * (p.Cout / 256);
-    if (p.products == 1) hipLaunchKernelGGL((conv_dma_kernel<256, true>), dim3(tiles), dim3(512), 0, stream, p);
-    else if (p.in2 && conv_line_order(p, DMA_WIDE_DUAL)) hipLaunchKernelGGL((conv_dma_kernel<256, false, 128, true, 3, 64, false, 1>), dim3(tiles), dim3(512), 0, stream, p);
-    else if (p.in2) hipLaunchKernelGGL((conv_dma_kernel<256, false, 128, true>), dim3(tiles), dim3(512), 0, stream, p);
-    else if (conv_line_order(p, DMA_WIDE)) hipLaunchKernelGGL((conv_dma_kernel<256, false, 128, false, 3, 64, false, 1>), dim3(tiles), dim3(512), 0, stream, p);
-    else hipLaunchKernelGGL(conv_dma_kernel<256>, dim3(tiles), dim3(512), 0, stream, p);
-    return ssg_check_hip(hipGetLastError(), "conv_dma_kernel");
+    if (dma && k.tall_mintiles > 0 && p.epi == 0 && tiles_tall >= k.tall_mintiles && (dual ? k.tall_dual != 0 : (!p.res || k.tall_res))) r.BM = 256;
+  } else {
+    // 128x128: round 2 measured it neutral (21.42 vs 21.46 k img/s); with the round-6 epilogue the layer2 entry launches gain (256 -> 128 1x1:
+    // 0.723 -> 0.653 ms, 128 -> 128 3x3 stride 2: 0.591 -> 0.523 ms per 1000 images; bit-identical, profiles/r06_ab_nt_policy.txt): on by default
+    dma = split && !cin4 && r.BN == 128 && (k.dma & 2) && p.epi == 0 && !dual;
+    if (!dma) r.BK = split ? (cin4 ? 16 : 32) : (dual ? 32 : 16);
   }
-  return launch_conv_bk<128, 256, 64, 64, false, 32, true>(p, stream);
+  if (!dma) return r;
+  r.family = CONV_DMA; r.BK = 16;
+  // Fetch order of the pixel operand (template parameter LINE).  The line order needs an even number of k-tiles and 32-channel runs in
+  // both inputs (every shape the two convolution entry points accept has them; the distance GEMMs of the source term come with any
+  // multiple of 16 and keep the k-tile order).  Unset, each instance runs the order that measured faster -- forward of 1000
+  // images, both orders interleaved in one process (profiles/r08_ab_conv_line_fetch.txt): 128 x 128 - 3 / - 6 %, 128 x 256 with a residual
+  // - 3 %, DUAL 0 ... - 2 %, 256 x 256 1x1 0 ... - 4 % and 3x3 - 5 %; the 256 x 256 DUAL instance was not timed and keeps the k-tile order.
+  if (p.epi != 0 || ((p.Kpad / 16) & 1) || (p.Cin % 32) || (dual && (p.Cin2 % 32))) r.line = 0;
+  else if (k.line >= 0) r.line = k.line;
+  else r.line = (r.BM == 256 && dual) ? 0 : 1;
+  return r;
+}
+// ---- end of routing
+
+static ConvKnobs read_conv_knobs() {
+  auto knob_int = [](const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; };
+  ConvKnobs k;
+  k.dma = knob_int("SSG_CONV_DMA", k.dma);
+  if (const char* e = getenv("SSG_CONV_LINE")) k.line = atoi(e) == 1 ? 1 : 0;
+  k.wide_mintiles = knob_int("SSG_SPLIT_WIDE_MINTILES", k.wide_mintiles);
+  k.bn64_maxtiles = knob_int("SSG_SPLIT_BN64_MAXTILES", k.bn64_maxtiles);
+  k.tall_mintiles = knob_int("SSG_CONV_TALL_MINTILES", k.tall_mintiles);
+  k.tall_res = knob_int("SSG_CONV_TALL_RES", k.tall_res);
+  k.tall_dual = knob_int("SSG_CONV_TALL_DUAL", k.tall_dual);
+  return k;
+}
+static const ConvKnobs& conv_knobs() { static const ConvKnobs k = read_conv_knobs(); return k; }
+
+template <int BM, int BN, bool DUAL>
+static int launch_conv_dma(const ConvParams& p, int line, hipStream_t stream) {
+  const int tiles = ((p.M + BM - 1) / BM) * (p.Cout / BN);
+  if (line) hipLaunchKernelGGL((conv_dma_kernel<BM, BN, DUAL, 1>), dim3(tiles), dim3((BM / 64) * (BN / 64) * 64), 0, stream, p);
+  else hipLaunchKernelGGL((conv_dma_kernel<BM, BN, DUAL, 0>), dim3(tiles), dim3((BM / 64) * (BN / 64) * 64), 0, stream, p);
+  return ssg_check_hip(hipGetLastError(), "conv_dma_kernel");
 }
 
-static bool conv_prefers_bn64(const ConvParams& p, bool split) {
-  static int maxtiles = -1;
-  if (maxtiles < 0) { const char* e = getenv("SSG_SPLIT_BN64_MAXTILES"); maxtiles = e ? atoi(e) : 300; }
-  if (!split) return false;
-  const int tiles = ((p.M + 127) / 128) * (p.Cout / 128);
-  return tiles < maxtiles;
+// the register-staged instances of a 128 x BN tile (BN = 128 or 64)
+template <int BN, int WN>
+static int launch_conv_igemm(const ConvParams& p, const ConvRoute& r, bool split, bool cin4, hipStream_t stream) {
+  if (cin4) return split ? launch_conv_bk<128, BN, 64, WN, true, 16, true>(p, stream) : launch_conv_bk<128, BN, 64, WN, true, 16, false>(p, stream);
+  if (split) return launch_conv_bk<128, BN, 64, WN, false, 32, true>(p, stream);
+  return r.BK == 32 ? launch_conv_bk<128, BN, 64, WN, false, 32, false>(p, stream) : launch_conv_bk<128, BN, 64, WN, false, 16, false>(p, stream);
+}
+
+// every convolution-GEMM launch of the library: the two entry points below, the float32 distance GEMMs and the source term's bound pass
+static int launch_conv(const ConvParams& p, bool split, bool cin4, hipStream_t stream) {
+  const ConvRoute r = conv_route(p, split, cin4, conv_knobs());
+  if (r.family == CONV_DMA) {
+    if (r.BM == 256) return r.dual ? launch_conv_dma<256, 256, true>(p, r.line, stream) : launch_conv_dma<256, 256, false>(p, r.line, stream);
+    if (r.BN == 256) return r.dual ? launch_conv_dma<128, 256, true>(p, r.line, stream) : launch_conv_dma<128, 256, false>(p, r.line, stream);
+    return launch_conv_dma<128, 128, false>(p, r.line, stream);
+  }
+  if (r.BN == 256) return launch_conv_bk<128, 256, 64, 64, false, 32, true>(p, stream);
+  return r.BN == 128 ? launch_conv_igemm<128, 64>(p, r, split, cin4, stream) : launch_conv_igemm<64, 32>(p, r, split, cin4, stream);
+}
+
+// The GEMM-shaped form  acc[i, j] = <x_i, y_j>  (x [m,d], y [n,d], d % 32 == 0): a 1x1 convolution over m one-pixel images with n output
+// channels.  The caller sets the epilogue (epi, rowterm, tilemin, acc_scale).
+static ConvParams conv_gemm_params(const float* x, const float* y, const float* bias, float* out, int m, int n, int d) {
+  ConvParams p;
+  p.in = x; p.w = y; p.bias = bias; p.out = out;
+  p.B = p.M = m; p.H = p.W = p.OH = p.OW = 1; p.Cin = p.Kpad = d; p.Cout = n; p.KH = p.KW = 1; p.stride = 1; p.pad = 0; p.relu = 0;
+  p.nk1 = d / 16; p.in_bytes = (unsigned)((int64_t)m * d * 4);
+  return p;
 }
 
 // Conv2d(bias folded from eval BatchNorm) + optional residual add + optional ReLU, NHWC fp32.
@@ -1479,18 +1321,12 @@ extern "C" int ssg_conv2d_nhwc_xt(const void* in, const void* w, const void* wt,
   const int64_t in_bytes = (int64_t)B * H * W * Cin * 4;
   if (in_bytes > 0x7fffffffLL) { ssg_set_error("ssg_conv2d_nhwc: input tensor of %lld bytes exceeds the 2 GiB buffer-resource range of this kernel; use a smaller batch", (long long)in_bytes); return SSG_ERR_INVALID; }
   p.in_bytes = (unsigned)in_bytes;
-  p.in2 = nullptr; p.H2 = p.W2 = p.Cin2 = 0; p.stride2 = 1; p.in2_bytes = 0; p.rowterm = nullptr; p.epi = 0; p.tilemin = nullptr; p.tmin_ld = 0;
   p.out_split = (flags & 2) ? 1 : 0; p.res_split = p.out_split; p.acc_scale = acc_scale;
-  static int variant = -1;
-  if (variant < 0) { const char* e = getenv("SSG_CONV_VARIANT"); variant = e ? atoi(e) : 0; }
-  p.variant = variant;
   const bool cin4 = (Cin == 4);
   p.Kpad = cin4 ? 32 * ((KH * KW + 7) / 8) : KH * KW * Cin;
   p.nk1 = p.Kpad / 16;   // no second input: every k-tile (of either BK) reads `in`
   { int rc; p.wt = (const float*)conv_tiled_weights("ssg_conv2d_nhwc_xt", w, wt, flags, Cout, p.Kpad, &rc); if (rc) return rc; }
-  if (cin4) return (Cout % 128 == 0) ? launch_conv<128, 128, 64, 64, true>(p, stream, split) : launch_conv<128, 64, 64, 32, true>(p, stream, split);
-  if (conv_prefers_wide(p, split)) return launch_conv_wide(p, stream);
-  return (Cout % 128 == 0 && !conv_prefers_bn64(p, split)) ? launch_conv<128, 128, 64, 64, false>(p, stream, split) : launch_conv<128, 64, 64, 32, false>(p, stream, split);
+  return launch_conv(p, split, cin4, stream);
 }
 
 extern "C" int ssg_conv2d_nhwc_x(const void* in, const void* w, const float* bias, const void* res, void* out, int B, int H, int W,
@@ -1513,7 +1349,7 @@ extern "C" int ssg_conv1x1_dual_nhwc_xt(const void* in, const void* in2, const v
                                         int32_t* overflow, hipStream_t stream) {
   ConvParams p;
   p.cscale = ch_scale; p.overflow = overflow;
-  p.in = (const float*)in; p.w = (const float*)w; p.bias = bias; p.res = nullptr; p.out = (float*)out;
+  p.in = (const float*)in; p.w = (const float*)w; p.bias = bias; p.out = (float*)out;
   p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.KH = 1; p.KW = 1; p.stride = 1; p.pad = 0; p.relu = relu;
   p.OH = H; p.OW = W;
   const int64_t M = (int64_t)B * H * W;
@@ -1525,12 +1361,11 @@ extern "C" int ssg_conv1x1_dual_nhwc_xt(const void* in, const void* in2, const v
   }
   p.M = (int)M; p.in_bytes = (unsigned)in_bytes;
   p.in2 = (const float*)in2; p.H2 = H2; p.W2 = W2; p.Cin2 = Cin2; p.stride2 = stride2; p.in2_bytes = (unsigned)in2_bytes;
-  p.Kpad = Cin + Cin2; p.nk1 = Cin / 32; p.variant = 0; p.rowterm = nullptr; p.epi = 0; p.tilemin = nullptr; p.tmin_ld = 0;   // dual input stays on BK=32 (nk1 counts 32-wide tiles)
+  p.Kpad = Cin + Cin2; p.nk1 = Cin / 32;   // dual input stays on BK=32 (nk1 counts 32-wide tiles)
   p.out_split = (flags & 2) ? 1 : 0; p.res_split = p.out_split; p.acc_scale = acc_scale;
   const bool split = (flags & 1) != 0;
   { int rc; p.wt = (const float*)conv_tiled_weights("ssg_conv1x1_dual_nhwc_xt", w, wt, flags, Cout, p.Kpad, &rc); if (rc) return rc; }
-  if (conv_prefers_wide(p, split)) return launch_conv_wide(p, stream);
-  return (Cout % 128 == 0 && !conv_prefers_bn64(p, split)) ? launch_conv<128, 128, 64, 64, false>(p, stream, split) : launch_conv<128, 64, 64, 32, false>(p, stream, split);
+  return launch_conv(p, split, false, stream);
 }
 
 extern "C" int ssg_conv1x1_dual_nhwc_x(const void* in, const void* in2, const void* w, const float* bias, void* out, int B, int H, int W,
@@ -1578,12 +1413,9 @@ extern "C" int ssg_pairwise_sqdist_f32(const float* x, const float* y, int m, in
   float* rowterm = ws; float* colterm = ws + m;
   hipLaunchKernelGGL(row_sqnorm_kernel, dim3((m + 3) / 4), dim3(256), 0, stream, x, m, d, self_form ? 2.f : 1.f, rowterm);
   hipLaunchKernelGGL(row_sqnorm_kernel, dim3((n + 3) / 4), dim3(256), 0, stream, y, n, d, self_form ? 0.f : 1.f, colterm);
-  ConvParams p;
-  p.in = x; p.w = y; p.bias = colterm; p.res = nullptr; p.out = out;
-  p.B = m; p.H = 1; p.W = 1; p.Cin = d; p.Cout = n; p.KH = 1; p.KW = 1; p.stride = 1; p.pad = 0; p.relu = 0; p.OH = 1; p.OW = 1;
-  p.M = m; p.Kpad = d; p.nk1 = d / 16; p.variant = 0; p.in_bytes = (unsigned)((int64_t)m * d * 4);
-  p.in2 = nullptr; p.H2 = p.W2 = p.Cin2 = 0; p.stride2 = 1; p.in2_bytes = 0; p.rowterm = rowterm; p.epi = 1; p.tilemin = nullptr; p.tmin_ld = 0; p.out_split = p.res_split = 0; p.acc_scale = 1.f;
-  return (n % 128 == 0) ? launch_conv<128, 128, 64, 64, false>(p, stream) : launch_conv<128, 64, 64, 32, false>(p, stream);
+  ConvParams p = conv_gemm_params(x, y, colterm, out, m, n, d);
+  p.rowterm = rowterm; p.epi = 1;
+  return launch_conv(p, false, false, stream);
 }
 
 // out[i,j] = 2 - 2 <x_i, y_j> in float32 (reid/rerank.py:174-182 original_dist of re_ranking_init).
@@ -1593,12 +1425,9 @@ extern "C" int ssg_cosine_dist_f32(const float* x, const float* y, int m, int n,
     ssg_set_error("ssg_cosine_dist_f32: need d %% 32 == 0, n %% 64 == 0 and x < 2 GiB (m=%d n=%d d=%d)", m, n, d);
     return SSG_ERR_INVALID;
   }
-  ConvParams p;
-  p.in = x; p.w = y; p.bias = zeros; p.res = nullptr; p.out = out;
-  p.B = m; p.H = 1; p.W = 1; p.Cin = d; p.Cout = n; p.KH = 1; p.KW = 1; p.stride = 1; p.pad = 0; p.relu = 0; p.OH = 1; p.OW = 1;
-  p.M = m; p.Kpad = d; p.nk1 = d / 16; p.variant = 0; p.in_bytes = (unsigned)((int64_t)m * d * 4);
-  p.in2 = nullptr; p.H2 = p.W2 = p.Cin2 = 0; p.stride2 = 1; p.in2_bytes = 0; p.rowterm = nullptr; p.epi = 2; p.tilemin = nullptr; p.tmin_ld = 0; p.out_split = p.res_split = 0; p.acc_scale = 1.f;
-  return (n % 128 == 0) ? launch_conv<128, 128, 64, 64, false>(p, stream) : launch_conv<128, 64, 64, 32, false>(p, stream);
+  ConvParams p = conv_gemm_params(x, y, zeros, out, m, n, d);
+  p.epi = 2;
+  return launch_conv(p, false, false, stream);
 }
 
 

@@ -176,15 +176,11 @@ static int source_rowmin_filtered_impl(const float* tgt, const float* src, int n
     hipLaunchKernelGGL(h8l8_encode_kernel, dim3(4096), dim3(256), 0, stream, src, ss, (int64_t)Ns_pad * d / 8, scale_s);
     gt = ts; gs = ss;
   }
-  ConvParams p;
-  p.in = gt; p.w = gs; p.bias = colterm; p.res = nullptr; p.out = nullptr;
-  p.B = nrows; p.H = 1; p.W = 1; p.Cin = d; p.Cout = Ns_pad; p.KH = 1; p.KW = 1; p.stride = 1; p.pad = 0; p.relu = 0; p.OH = 1; p.OW = 1;
-  p.M = nrows; p.Kpad = d; p.nk1 = d / 16; p.variant = 0; p.in_bytes = (unsigned)((int64_t)nrows * d * 4);
-  p.in2 = nullptr; p.H2 = p.W2 = p.Cin2 = 0; p.stride2 = 1; p.in2_bytes = 0; p.rowterm = rowterm; p.epi = 3; p.tilemin = tilemin; p.tmin_ld = ntiles; p.out_split = p.res_split = 0;
+  ConvParams p = conv_gemm_params(gt, gs, colterm, nullptr, nrows, Ns_pad, d);
+  p.rowterm = rowterm; p.epi = 3; p.tilemin = tilemin; p.tmin_ld = ntiles;
   p.acc_scale = split ? 1.f / (scale_t * scale_s) : 1.f;
-  // 128x256 tiles when the padded source count allows: 3/4 of the global->LDS bytes of the 128x128 tile
-  int rc = split ? ((Ns_pad % 256) == 0 ? launch_conv_wide(p, stream) : launch_conv_bk<128, 128, 64, 64, false, 32, true>(p, stream))
-                 : launch_conv<128, 128, 64, 64, false>(p, stream);
+  // (epi 3: 128x256 tiles when the padded source count allows -- 3/4 of the global->LDS bytes of the 128x128 tile)
+  int rc = launch_conv(p, split, false, stream);
   if (rc) return rc;
   hipLaunchKernelGGL(source_refine_kernel<8>, dim3((nrows + 3) / 4), dim3(256), 0, stream, tgt, src, tilemin, ntiles, ntiles, tol, nrows, Ns, d, rowmin);
   SSG_LAUNCH_CHECK("source_refine_kernel");

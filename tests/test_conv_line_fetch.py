@@ -28,7 +28,7 @@ def _child(mode, routing, line, dma=None):
     key = (mode, routing, line, dma)
     if key not in _RESULTS:
         env = dict(os.environ, **{"wide": _WIDE, "tall": _TALL, "default": {}}[routing])
-        for k in ("SSG_CONV_DMA", "SSG_SPLIT_BK16", "SSG_CONV_TALL_WM", "SSG_CONV_TALL_STAGES", "SSG_CONV_VARIANT", "SSG_CONV_LINE"):
+        for k in ("SSG_CONV_DMA", "SSG_CONV_LINE"):
             env.pop(k, None)
         if line is not None:
             env["SSG_CONV_LINE"] = line
@@ -60,7 +60,7 @@ def test_line_order_equals_the_register_staged_kernel(case):
 
 def test_odd_ktile_count_is_refused_by_the_entry_points():
     """Kpad / 16 odd needs Cin % 32 == 16: neither convolution entry point accepts such a shape (nothing is launched), so the line order
-    never meets an odd k-tile count there; the launchers check the parity all the same (conv_line_order)."""
+    never meets an odd k-tile count there; conv_route checks the parity all the same."""
     L = _lib.lib()
     w = torch.ones((256, 48), dtype=torch.int32, device="cuda")
     assert L.ssg_conv2d_nhwc_xt(None, ptr(w), None, None, None, None, 3, 16, 8, 48, 256, 1, 1, 1, 0, 1, 3, 1.0, None, None, None) == -1

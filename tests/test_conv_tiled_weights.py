@@ -68,8 +68,7 @@ _RESULTS = {}
 def _child(config):
     if config not in _RESULTS:
         env = dict(os.environ, **_ENV[config])
-        for k in ("SSG_CONV_DMA", "SSG_SPLIT_BK16", "SSG_CONV_TALL_WM", "SSG_CONV_TALL_STAGES", "SSG_CONV_VARIANT"):
-            env.pop(k, None)
+        env.pop("SSG_CONV_DMA", None)
         r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "conv_tiled_child.py")], capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
         assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
         _RESULTS[config] = json.loads(r.stdout.strip().splitlines()[-1])

@@ -894,7 +894,7 @@ def test_conv_split_half_vs_fp64(cfg, L, dev):
     (400, 16, 8, 512, 512, 3, 2, 1, False),        # layer4 first block: 3x3 stride 2
 ])
 def test_conv_tile_shapes_agree_bitwise(cfg, L, dev):
-    """The tile shape is a launch-time choice (conv.hip launch_conv_wide: 256 x 256 tiles with four LDS stages when at least 200
+    """The tile shape is a launch-time choice (conv.hip conv_route: 256 x 256 tiles with four LDS stages when at least 200
     of them exist, 128 x 256 / 128 x 128 tiles with three stages below that); every output element's reduction order is the same
     in all of them, so a large batch (tall tiles) must equal the same images run in small batches (short tiles) bit for bit.  The
     parity tests against the reference model use a handful of images and never reach the tall tiles."""
@@ -1042,7 +1042,7 @@ def test_conv_pair_matches_the_two_launches(M, L, dev):
 ])
 def test_conv_dual_tile_shapes_agree_bitwise(cfg, L, dev):
     """the DUAL instantiation (conv3 | downsample as one GEMM over the concatenated K, ssg_conv1x1_dual_nhwc_x) --
-    a large batch (conv_dma_kernel<256, false, 128, true>, 128 x 256 tiles) must equal the same images in small batches (the
+    a large batch (conv_dma_kernel<128, 256, true>, 128 x 256 tiles) must equal the same images in small batches (the
     register-staged kernel on short tiles) bit for bit, twice in a row (the LDS-DMA race of round 3 showed up run to run), and a
     float64 convolution of two images."""
     from ssg_amd._lib import check, ptr, stream

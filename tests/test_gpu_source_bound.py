@@ -8,7 +8,7 @@ sources -- is within tol / 2 of the true minimum of its granule.  Checked for ev
     gran8     the same kernel with 8-source granules everywhere          (SSG_SB_GRAN=8)
     nodma     the register-staged source_bound_kernel                    (SSG_SB_DMA=0)
     unfused   separate norm and conversion launches                      (SSG_SB_FUSED_ENC=0)
-    split     three products on split-half operands: conv_dma_kernel<256> when Ns_pad % 256 == 0, conv_igemm_kernel 128 x 128 otherwise
+    split     three products on split-half operands: conv_dma_kernel<128, 256> when Ns_pad % 256 == 0, conv_igemm_kernel 128 x 128 otherwise
     f32       float32 MFMA, conv_igemm_kernel
 
 The first four are one child process each (the knobs are cached per process, tests/source_bound_child.py); split and f32 are selected by

@@ -4,8 +4,10 @@ variant, round-robin, with HIP events around every C-ABI launch -- run-to-run an
 
 usage: ab_inproc.py [--B 1000] [--reps 6] name=lib.so[,ENV=VAL,...] ...
 Each variant gets its own dlopen'ed copy of the library (its `static` knob caches are read under its own environment at the first call).
-Run-time knobs are compared on ONE build (`new=lib.so line0=lib.so,SSG_CONV_LINE=0`: the pixel fetch order of conv_dma_kernel).
-Compile-time knobs (`-DSSG_CONV_WT=0`: row-major weight stages, `-DSSG_DMA_BPOS=...`) are compared as two builds of csrc/ssg_hip.hip."""
+Run-time knobs are compared on ONE build (`new=lib.so line0=lib.so,SSG_CONV_LINE=0`: the pixel fetch order of conv_dma_kernel;
+`tall0=lib.so,SSG_CONV_TALL_MINTILES=0`: no 256 x 256 tiles).  Two builds of csrc/ssg_hip.hip -- another commit, or a compile-time switch
+such as the epilogue cache policies `-DSSG_DMA_RES_AUX=...` -- are compared as two libraries; the same library under two names measures the
+noise floor of the comparison (`base=old.so base2=old.so new=lib.so`)."""
 import argparse
 import ctypes
 import os

@@ -33,9 +33,8 @@ static void run(const char* name, int B, int H, int W, int Cin, int Cout, int k,
   ConvParams p;
   p.in = (const float*)x; p.w = (const float*)w; p.bias = bi; p.res = res ? (const float*)r : nullptr; p.out = (float*)out;
   p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.OH = H; p.OW = W; p.Cout = Cout; p.KH = k; p.KW = k; p.stride = 1; p.pad = pad; p.relu = 1;
-  p.M = M; p.Kpad = Kpad; p.variant = 0; p.in_bytes = (unsigned)((size_t)M * Cin * 4);
-  p.in2 = nullptr; p.H2 = p.W2 = p.Cin2 = 0; p.stride2 = 1; p.nk1 = Kpad / 16; p.in2_bytes = 0; p.rowterm = nullptr; p.epi = 0; p.tilemin = nullptr; p.tmin_ld = 0;
-  p.out_split = 1; p.res_split = 1; p.acc_scale = 1.f; p.cscale = cs; p.overflow = ovf; p.products = 3; p.prof = prof;
+  p.M = M; p.Kpad = Kpad; p.nk1 = Kpad / 16; p.in_bytes = (unsigned)((size_t)M * Cin * 4);
+  p.out_split = 1; p.res_split = 1; p.cscale = cs; p.overflow = ovf; p.prof = prof;
   hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
   float best = 1e9f;
   for (int rep = 0; rep < 5; rep++) {
@@ -57,10 +56,10 @@ static void run(const char* name, int B, int H, int W, int Cin, int Cout, int k,
 int main(int argc, char** argv) {
   using namespace ssg;
   const int B = argc > 1 ? atoi(argv[1]) : 1000;
-  run("layer3 conv3 + res, 128x256", B, 16, 8, 256, 1024, 1, 0, true, 128, [](const ConvParams& p, int tiles) { hipLaunchKernelGGL(conv_dma_kernel<256>, dim3(tiles), dim3(512), 0, 0, p); });
-  run("layer3 conv3 + res, 256x256", B, 16, 8, 256, 1024, 1, 0, true, 256, [](const ConvParams& p, int tiles) { hipLaunchKernelGGL((conv_dma_kernel<256, false, 256, false, 4>), dim3(tiles), dim3(1024), 0, 0, p); });
-  run("layer3 conv1, 256x256", B, 16, 8, 1024, 256, 1, 0, false, 256, [](const ConvParams& p, int tiles) { hipLaunchKernelGGL((conv_dma_kernel<256, false, 256, false, 4>), dim3(tiles), dim3(1024), 0, 0, p); });
-  run("layer3 3x3, 256x256", B, 16, 8, 256, 256, 3, 1, false, 256, [](const ConvParams& p, int tiles) { hipLaunchKernelGGL((conv_dma_kernel<256, false, 256, false, 4>), dim3(tiles), dim3(1024), 0, 0, p); });
-  run("layer4 conv3 + res, 128x256", B, 8, 4, 512, 2048, 1, 0, true, 128, [](const ConvParams& p, int tiles) { hipLaunchKernelGGL(conv_dma_kernel<256>, dim3(tiles), dim3(512), 0, 0, p); });
+  run("layer3 conv3 + res, 128x256", B, 16, 8, 256, 1024, 1, 0, true, 128, [](const ConvParams& p, int tiles) { hipLaunchKernelGGL((conv_dma_kernel<128, 256>), dim3(tiles), dim3(512), 0, 0, p); });
+  run("layer3 conv3 + res, 256x256", B, 16, 8, 256, 1024, 1, 0, true, 256, [](const ConvParams& p, int tiles) { hipLaunchKernelGGL((conv_dma_kernel<256, 256>), dim3(tiles), dim3(1024), 0, 0, p); });
+  run("layer3 conv1, 256x256", B, 16, 8, 1024, 256, 1, 0, false, 256, [](const ConvParams& p, int tiles) { hipLaunchKernelGGL((conv_dma_kernel<256, 256>), dim3(tiles), dim3(1024), 0, 0, p); });
+  run("layer3 3x3, 256x256", B, 16, 8, 256, 256, 3, 1, false, 256, [](const ConvParams& p, int tiles) { hipLaunchKernelGGL((conv_dma_kernel<256, 256>), dim3(tiles), dim3(1024), 0, 0, p); });
+  run("layer4 conv3 + res, 128x256", B, 8, 4, 512, 2048, 1, 0, true, 128, [](const ConvParams& p, int tiles) { hipLaunchKernelGGL((conv_dma_kernel<128, 256>), dim3(tiles), dim3(512), 0, 0, p); });
   return 0;
 }
