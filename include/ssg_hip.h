@@ -60,8 +60,11 @@ int ssg_sqdist_self_f16(const float* x, const double* norms, int N, int d, int r
                         ssg_stream_t stream);
 /* The same matrix as an EXACT integer Gram on the int8 matrix cores (csrc/gram_i8.hip): for half-rounded features in
  * [-1, 1] (L2-normalised embeddings) feat*2^24 is an integer and scipy's float64 squared distance is exact, so
- * d2*2^48 = |X_i|^2 + |X_j|^2 - 2<X_i,X_j> in int64, with the dot product on v_mfma_i32_32x32x32_i8 over ndigits balanced
- * radix-256 digits (3: |feat| <= 0.498, 9 digit products; 4: |feat| <= 1, 16), gives the identical value.
+ * d2*2^48 = |X_i|^2 + |X_j|^2 - 2<X_i,X_j> as an integer, with the dot product on v_mfma_i32_32x32x32_i8 over ndigits balanced
+ * radix-256 digits (3: -0.50195 <= feat <= 0.4978, 9 digit products; 4: |feat| <= 1, 16), gives the identical value.
+ * The integer is exact for every admitted input: up to 4 d * 2^48 = 2^64 at d = 16384, combined modulo 2^64 (2^64 itself saturates;
+ * half holds nothing above 65504 anyway).  For d2 < 32 D is the reference's bit for bit; beyond, it is sqrt -> half -> square -> half
+ * of the correctly rounded float64 of that exact integer, where scipy's running float64 sum may round differently in the last bit.
  * ssg_gram_i8_encode writes the digits (ssg_gram_i8_encoded_bytes bytes: whole 64-row panels, layout [row / 64][k block][row % 64]
  * [digit][32] since round 4 -- opaque to the caller, consumed by ssg_sqdist_self_i8 only) and the exact int64 norms and sets *flag when a
  * feature does not fit (caller zeroes *flag first and falls back to ssg_sqdist_self_f16 when it is set;

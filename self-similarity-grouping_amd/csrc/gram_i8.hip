@@ -5,7 +5,7 @@
 // 2^-24, so X = feat * 2^24 is an integer with |X| <= 2^24, every term (x - y)^2 of cdist's sum is a multiple of 2^-48
 // below 4, and the float64 running sum never needs more than 51 bits: scipy's squared distance is EXACT.  The same
 // exact number comes out of integer arithmetic:
-//     d2 * 2^48 = |X_i|^2 + |X_j|^2 - 2 <X_i, X_j>            (int64, < 2^51)
+//     d2 * 2^48 = |X_i|^2 + |X_j|^2 - 2 <X_i, X_j>            (< 2^51 for d2 < 4; up to 4 d * 2^48 <= 2^64 in general: int64 below d = 8192, modulo 2^64 from there)
 // and the dot product runs on v_mfma_i32_32x32x32_i8 (2x the fp16 rate, 64x the fp64 MFMA rate per multiply) after
 // splitting X into NL balanced radix-256 digits  X = sum_a 256^a e_a,  e_a in [-128, 127]:
 //     <X, Y> = sum_w 256^w T_w,   T_w = sum_{a+b=w} sum_k ea_k fb_k        (NL^2 digit products, 2 NL - 1 int32 accumulators;
@@ -14,8 +14,10 @@
 // |feat| <= 1 (16 MFMAs).  The epilogue is the float64 one of pairwise.hip (sqrt -> half -> square -> half,
 // rerank.py:61-62) on the exactly converted integer, so D is bit-identical to the reference by construction (not just
 // with high probability) whenever d2 < 32 -- always true for L2-normalised rows (d2 <= 4); for un-normalised features in
-// [-1, 1] with larger distances both scipy's running sum and the int64 -> float64 conversion round in the last bit, like
-// the fp64 kernel.  Anything larger than 1 (or non-finite) is left to the fp64-MFMA kernel of pairwise.hip: the
+// [-1, 1] with larger distances both scipy's running sum and the integer -> float64 conversion round in the last bit, like
+// the fp64 kernel; the integer itself stays exact up to d2 = 65536 (d = 16384, antipodal rows of +-1: inf in half), and the
+// result is sqrt -> half -> square -> half of its correctly rounded float64 (tests/gram_i8_ref.py, tests/test_gpu_gram_i8.py).
+// Anything larger than 1 (or non-finite) is left to the fp64-MFMA kernel of pairwise.hip: the
 // caller picks NL from max|feat|; the encoder additionally raises a device flag if a digit does not fit.
 #include "ssg_common.h"
 #ifndef SSG_GI_NT_STORE
@@ -160,8 +162,16 @@ __device__ __forceinline__ bool gi_pick_tile(int M, int N, int symmetric, int sb
   return true;
 }
 
+// The epilogue's exact integer U = nA + nB - 2 dot = d2 * 2^48 (nA, nB: squared norms, up to d * 2^48 = 2^62; |dot| <= 2^62).
+// U <= 4 d * 2^48: below d = 8192 it fits int64 (WIDE = false: the kernels every embedding width runs, the same code as before the wide
+// form existed).  From d = 8192 on it reaches 2^63 -- antipodal rows of +-1 -- and 2^64 at d = 16384 (WIDE = true, kernels of their own,
+// launched from GI_WIDE_NKB k blocks on): the sum is taken modulo 2^64, which is U itself for every U < 2^64, and U == 2^64 (both
+// norms 2^62, dot = -2^62) is the only nonzero U that comes out as 0 -- told apart by dot < 0 and replaced by 2^64 - 1, which float64
+// rounds to 2^64.  (An int64 sum wrapped there and the clamp made it a distance of 0: 32768 and inf in the reference.)
+constexpr int GI_WIDE_NKB = 8192 / 32;              // k blocks from which U may not fit int64 (d > 8160)
+
 // sqrt -> half -> square -> half of the exact integer distance, D store (+ the mirrored half tile through an LDS patch), row maxima
-template <int NL>
+template <int NL, bool WIDE>
 __device__ __forceinline__ void gi_epilogue(v16i (&acc)[2 * NL - 1], unsigned char* lds, const long long* __restrict__ nA, const long long* __restrict__ nB, int M, int N,
                                             int rowA0, hbits* __restrict__ D, unsigned* __restrict__ rowmax, int symmetric, int tm, int tn, bool mirror) {
   constexpr int NACC = 2 * NL - 1;
@@ -189,17 +199,33 @@ __device__ __forceinline__ void gi_epilogue(v16i (&acc)[2 * NL - 1], unsigned ch
       long long dot = 0;
 #pragma unroll
       for (int w = NACC - 1; w >= 0; w--) dot = dot * 256 + (long long)acc[w][r];
-      long long d2i = nA[li] + nj - 2 * dot;           // exact squared distance in units of 2^-48
+      if constexpr (!WIDE) {
+      long long d2i = nA[li] + nj - 2 * dot;           // exact squared distance in units of 2^-48 (< 2^63: d <= 8160)
       if (d2i < 0 || rowA0 + li == gj) d2i = 0;         // cannot be negative; cdist(x, x) diagonal is exactly 0
       if (d2i < (1LL << 50) && !(symmetric & 2)) {
         const hbits hh = sqrt_units48_to_half(d2i);      // == d2h(sqrt((double)d2i * 2^-48)) for d2 < 4: every L2-normalised pair
         dd = h_mul(hh, hh);                              // np.power(half, 2) rerank.py:62
       } else {
-        const double s = (double)d2i * 3.5527136788005009e-15;   // 2^-48, exact (d2i < 2^53)
+        // 2^-48 scales exactly; the conversion is exact for d2i < 2^53 (d2 < 32) and rounds to nearest even beyond, like numpy's
+        const double s = (double)d2i * 3.5527136788005009e-15;
         const double sq = sqrt(s);
         const hbits hh = d2h(sq);                         // cdist(...).astype(float16)   rerank.py:61
         // np.power(half, 2) rerank.py:62; MemorySave branch (:49-59): np.power(cdist, 2).astype(float16), one rounding
         dd = (symmetric & 2) ? d2h(sq * sq) : h_mul(hh, hh);
+      }
+      } else {
+      unsigned long long d2u = (unsigned long long)nA[li] + (unsigned long long)nj - 2ull * (unsigned long long)dot;     // U modulo 2^64
+      if (rowA0 + li == gj) d2u = 0;
+      else if (d2u == 0 && dot < 0) d2u = ~0ull;        // U == 2^64 -> 2^64 - 1: the same float64
+      if (d2u < (1ull << 50) && !(symmetric & 2)) {
+        const hbits hh = sqrt_units48_to_half((long long)d2u);
+        dd = h_mul(hh, hh);
+      } else {
+        const double s = (double)d2u * 3.5527136788005009e-15;
+        const double sq = sqrt(s);
+        const hbits hh = d2h(sq);
+        dd = (symmetric & 2) ? d2h(sq * sq) : h_mul(hh, hh);
+      }
       }
       cmax = cmax > dd ? cmax : dd;
     }
@@ -254,7 +280,7 @@ __device__ __forceinline__ void gi_epilogue(v16i (&acc)[2 * NL - 1], unsigned ch
 
 // D[i,j] = half(half(sqrt(d2))^2) for rows [rowA0, rowA0+M) x all N columns, atomicMax rowmax.  EA = encoded rows of the
 // row block, EB = encoded rows of the whole set.  symmetric: only tiles on/above the diagonal are launched, mirrored on store.
-template <int NL, int KB2>
+template <int NL, int KB2, bool WIDE>
 __global__ __launch_bounds__(256, 2) void gram_i8_kernel(const int8_t* __restrict__ EA, const int8_t* __restrict__ EB,
                                                          const long long* __restrict__ nA, const long long* __restrict__ nB, int M, int N, int nkb,
                                                          int rowA0, hbits* __restrict__ D, unsigned* __restrict__ rowmax, int symmetric,
@@ -349,7 +375,7 @@ __global__ __launch_bounds__(256, 2) void gram_i8_kernel(const int8_t* __restric
     if (sum_ == 0x7fffffff) D[0] = (hbits)sum_;
     return; }
 #endif
-  gi_epilogue<NL>(acc, lds, nA, nB, M, N, rowA0, D, rowmax, symmetric, tm, tn, mirror);
+  gi_epilogue<NL, WIDE>(acc, lds, nA, nB, M, N, rowA0, D, rowmax, symmetric, tm, tn, mirror);
 }
 
 
@@ -368,7 +394,7 @@ __device__ __forceinline__ void gi_dma3(__amdgpu_buffer_rsrc_t rs, unsigned char
   __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, SSG_GI_LDSP(l1), 16, g1, 0, 0, 0);
   __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, SSG_GI_LDSP(l2), 16, g2, 0, 0, 0);
 }
-template <int NL, int NS>
+template <int NL, int NS, bool WIDE>
 __global__ __launch_bounds__(256, NS == 3 ? 4 : 3) void gram_i8_dma_kernel(const int8_t* __restrict__ E, unsigned e_bytes, const long long* __restrict__ nA, const long long* __restrict__ nB,
                                                              int M, int N, int nkb, int rowA0, hbits* __restrict__ D, unsigned* __restrict__ rowmax, int symmetric,
                                                              const int* __restrict__ flag, int sb) {
@@ -451,7 +477,7 @@ __global__ __launch_bounds__(256, NS == 3 ? 4 : 3) void gram_i8_dma_kernel(const
 #undef SSG_GI_DMA
 #undef SSG_GI_MMA
 #undef SSG_GI_PUBLISH
-  gi_epilogue<NL>(acc, st0, nA, nB, M, N, rowA0, D, rowmax, symmetric, tm, tn, mirror);
+  gi_epilogue<NL, WIDE>(acc, st0, nA, nB, M, N, rowA0, D, rowmax, symmetric, tm, tn, mirror);
 }
 
 }  // namespace ssg
@@ -504,11 +530,12 @@ extern "C" int ssg_sqdist_self_i8(const void* E, const int64_t* norms, int N, in
   const int64_t tiles = symmetric ? (sb ? nbk * (nbk + 1) / 2 * sb * sb : (int64_t)T * (T + 1) / 2) : (int64_t)((nrows + GI_T - 1) / GI_T) * T;
   if (tiles > 0x7fffffff) { ssg_set_error("ssg_sqdist_self_i8: too many tiles"); return SSG_ERR_INVALID; }
   const int8_t* e = (const int8_t*)E;
-#define SSG_GI_LAUNCH(NL_, KB_) hipLaunchKernelGGL((gram_i8_kernel<NL_, KB_>), dim3((unsigned)tiles), dim3(256), 0, stream, e, e, \
+  const bool wide = nkb >= GI_WIDE_NKB;            // d2 * 2^48 may not fit int64: the kernels with the modulo-2^64 epilogue
+#define SSG_GI_LAUNCH(NL_, KB_) hipLaunchKernelGGL((wide ? gram_i8_kernel<NL_, KB_, true> : gram_i8_kernel<NL_, KB_, false>), dim3((unsigned)tiles), dim3(256), 0, stream, e, e, \
     (const long long*)norms + row0, (const long long*)norms, nrows, N, nkb, row0, D, rowmax, symmetric | (memory_save ? 2 : 0), flag, sb)
   if (gi_use_dma(N, d, ndigits)) {
     const unsigned e_bytes = (unsigned)ssg_gram_i8_encoded_bytes(N, d, ndigits);
-#define SSG_GI_DMA_LAUNCH(NS_) hipLaunchKernelGGL((gram_i8_dma_kernel<3, NS_>), dim3((unsigned)tiles), dim3(256), 0, stream, e, e_bytes, (const long long*)norms + row0, \
+#define SSG_GI_DMA_LAUNCH(NS_) hipLaunchKernelGGL((wide ? gram_i8_dma_kernel<3, NS_, true> : gram_i8_dma_kernel<3, NS_, false>), dim3((unsigned)tiles), dim3(256), 0, stream, e, e_bytes, (const long long*)norms + row0, \
       (const long long*)norms, nrows, N, nkb, row0, D, rowmax, symmetric | (memory_save ? 2 : 0), flag, sb)
     const char* s_ = getenv("SSG_I8_DMA_STAGES");      // 3 (default): 36 KB, four workgroups per CU; 4: 48 KB, three
     if (s_ && atoi(s_) == 4) SSG_GI_DMA_LAUNCH(4); else SSG_GI_DMA_LAUNCH(3);

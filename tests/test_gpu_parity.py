@@ -1494,10 +1494,11 @@ def test_evaluator_dropin(golden, dev):
 # ------------------------------------------------------------------ original distance: int8 exact Gram / fp64 fallback
 @pytest.mark.parametrize("case", [
     # name, N, d, feature scale, env
-    ("i8_3digits", 700, 128, 1.0, {}),                                   # unit-norm rows: |feat| <= 0.49 -> 3 digits, 2 k blocks per stage
-    ("i8_3digits_odd_blocks", 300, 72, 1.0, {}),                         # d = 72 -> 3 k blocks (one per stage), zero-padded last block
-    ("i8_4digits_forced", 500, 64, 1.0, {"SSG_SELF_GRAM_DIGITS": "4"}),
-    ("i8_4digits_auto", 400, 40, 3.0, {}),                               # max |feat| in (0.49, 1]
+    ("i8_3digits", 700, 128, 1.0, {}),                                   # unit-norm rows: |feat| <= 0.49 -> 3 digits; 4 k blocks -> LDS-DMA kernel, 3 stages, tail 1
+    ("i8_3digits_odd_blocks", 300, 72, 1.0, {}),                         # d = 72, padded to 96 by the caller -> 3 k blocks: register-staged kernel, one block per stage (odd count)
+    ("i8_4digits_forced", 500, 64, 1.0, {"SSG_SELF_GRAM_DIGITS": "4"}),  # 4 digits: always the register-staged kernel (2 stages)
+    ("i8_4digits_auto", 400, 40, 3.0, {}),                               # max |feat| in (0.49, 1]; d padded to 64 by the caller: 2 stages
+    # (every other variant, tail, tile order and stripe: tests/test_gpu_gram_i8.py)
     ("fp64_fallback_range", 400, 64, 9.0, {}),                           # |feat| > 1: the integer path does not apply
     ("fp64_forced", 500, 96, 1.0, {"SSG_SELF_GRAM": "f64"}),
 ])
