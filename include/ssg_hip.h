@@ -185,9 +185,7 @@ int ssg_eps_sample_hist(const void* M, const uint16_t* v, int N, int row0, int n
  * hist2x = 2 x 4097 words and tickets2 = 2 words, zeroed by the caller; thr5 (5 words) ends up as ssg_eps_select_threshold followed by
  * ssg_eps_refine_threshold leave it (the separate calls remain: the sharded two-call form all-reduces the histograms in between) */
 int ssg_eps_sample_threshold(const void* M, const uint16_t* v, int N, int row0, int nrows, int mode, double lambda_value, int row_stride,
-                             double quantile, uint64_t* hist2x, uint64_t* thr5, uint32_t* tickets2, uint64_t* splitters1023, ssg_stream_t stream);
-/* splitters1023 (nullable): 1023 ascending float64 bit patterns that cut the values below the threshold into 1024 parts of about equal sample
- * mass (interpolated in the level-1 histogram) -- the splitters of ssg_samplesort_u64_presplit_dev for the keys the compaction pass collects */
+                             double quantile, uint64_t* hist2x, uint64_t* thr5, uint32_t* tickets2, ssg_stream_t stream);
 int ssg_eps_select_threshold(const uint64_t* hist, double quantile, uint64_t* thr3, ssg_stream_t stream);
 /* second level: ssg_eps_sample_hist(..., refine = thr, hist2) counts the sample elements of the selected coarse bin in 1024 linear
  * sub-bins (hist2 zeroed by the caller); this replaces thr[0] by the sub-bin edge (one guard sub-bin) */
@@ -225,10 +223,6 @@ int ssg_samplesort_u64_dev(uint64_t* buf, uint64_t n_cap, const uint64_t* n_dev,
  * whole array took 7.1 ms.  Same contract as ssg_samplesort_u64_dev (*fail = 1: a bucket beyond 16 384 keys), its own workspace size. */
 size_t ssg_samplesort_u64_big_workspace_bytes(uint64_t n_cap);
 int ssg_samplesort_u64_big_dev(uint64_t* buf, uint64_t n_cap, const uint64_t* n_dev, void* ws, size_t ws_bytes, uint64_t* fail, ssg_stream_t stream);
-/* round 6: the same sort on 1023 ascending splitters the caller already holds on the device (any monotone splitters sort correctly; balance is
- * the caller's business: a bucket beyond 16 384 keys sets *fail): three launches, no sample sort.  gcount2048 (2048 uint32) and *fail: zero on entry */
-int ssg_samplesort_u64_presplit_dev(uint64_t* buf, uint64_t n_cap, const uint64_t* n_dev, const uint64_t* splitters1023, uint32_t* gcount2048,
-                                    void* ws, size_t ws_bytes, uint64_t* fail, ssg_stream_t stream);
 size_t ssg_eps_mean_workspace_bytes(int64_t top);
 /* out2[0] = mean of the first `top` sorted keys with numpy's pairwise summation (mode 0: f64;
  * mode 1: float32 sum of half values -> half, out2[1] = its bits) */

@@ -12,6 +12,7 @@ among their core neighbours; noise = -1).  It accepts a numpy/torch matrix, or t
 """
 import math
 import numbers
+import os
 
 import numpy as np
 import torch
@@ -51,6 +52,72 @@ def as_handle(X, device=None):
     raise TypeError("unsupported distance matrix type %r" % type(X))
 
 
+def _sampled_path():
+    """SSG_EPS_PATH: 'sampled' (default) = the sampled threshold + one full pass; anything else = the radix select only"""
+    return os.environ.get("SSG_EPS_PATH", "sampled") == "sampled"
+
+
+def _sparse(h):
+    """the sparse copy S of J' a re-rank handle carries (mode 0 only), or None"""
+    return getattr(h, "sparse", None) if h.mode == 0 else None
+
+
+def _compact_below(L, h, thr3, buf, n_cap, cursor, st, rowmask=None):
+    """The eps rule's one full pass: the keys below the threshold thr3 -> buf; cursor = 3 zeroed words {keys, exact zeros, dense pass needed}.
+    With a sparse copy S of J': row by row through S where the threshold lies below the row's floor (decided on the device; the dense pass
+    for the other rows is queued behind it), the row mask in the handle's workspace or in `rowmask`; without S: the dense pass."""
+    sp = _sparse(h)
+    if sp is not None:
+        check(L.ssg_eps_compact_below_s(ptr(h.M), ptr(h.v), h.N, h.row0, h.nrows, h.lambda_value, ptr(thr3), ptr(buf), n_cap, ptr(cursor), ptr(sp["pool"]),
+                                        ptr(sp["seg_off"]), ptr(sp["seg_len"]), sp["nseg"], ptr(sp["cursor"]), ptr(sp["vmin"]), sp["jp0"],
+                                        ptr(sp["rowmask"] if rowmask is None else rowmask), st), "ssg_eps_compact_below_s")
+    else:
+        check(L.ssg_eps_compact_below(ptr(h.M), ptr(h.v), h.N, h.row0, h.nrows, h.mode, h.lambda_value, ptr(thr3), ptr(buf), n_cap, ptr(cursor), st),
+              "ssg_eps_compact_below")
+
+
+def _region_query(L, h, eps, cnt, edges, cap, cursor, st, rowmask=None):
+    """Region query of the handle's rows: neighbour counts -> cnt, hits -> edges (capacity cap); cursor = 2 zeroed words {edges counted, dense
+    pass needed}.  eps is a float, or a device tensor whose first float64 the eps rule queued in front leaves (the `_dev` entries).  With a
+    sparse copy S of J': row by row through S where eps lies below the row's floor (decided on the device), dense scan of the rest."""
+    on_dev = torch.is_tensor(eps)
+    e = ptr(eps) if on_dev else float(eps)
+    sp = _sparse(h)
+    if sp is not None:
+        fn, name = (L.ssg_region_query_s_dev, "ssg_region_query_s_dev") if on_dev else (L.ssg_region_query_s, "ssg_region_query_s")
+        check(fn(ptr(h.M), ptr(h.v), h.N, h.row0, h.nrows, h.lambda_value, e, ptr(sp["pool"]), ptr(sp["seg_off"]), ptr(sp["seg_len"]), sp["nseg"],
+                 ptr(sp["cursor"]), ptr(sp["vmin"]), sp["jp0"], ptr(sp["rowmask"] if rowmask is None else rowmask), ptr(cnt), ptr(edges), cap,
+                 ptr(cursor), st), name)
+    else:
+        fn, name = (L.ssg_region_query_dev, "ssg_region_query_dev") if on_dev else (L.ssg_region_query, "ssg_region_query")
+        check(fn(ptr(h.M), ptr(h.v), h.N, h.row0, h.nrows, h.mode, h.lambda_value, e, ptr(cnt), ptr(edges), cap, ptr(cursor), st), name)
+
+
+def _sort_kind(expect):
+    """Which sort orders `expect` candidates of the fused chain: the sample sort (4 launches) while its 1024 sorting buckets stay LDS-sized
+    -- a bucket may run to 4x the mean, 2048 keys fit -> up to 4e5 candidates (N = 16 000: 2.7e5); the 4095-splitter geometry with buckets
+    of up to 16 384 keys in 128 KB of LDS from 4e6 to 2.4e7 (N = 128 000: 1.7e7 candidates: 3.0 ms against 6.9 of the network; measured
+    slower than the network below ~4e6 keys -- tools/time_sort.py -- so N = 30 000's 9.4e5 candidates keep the network); otherwise, and
+    always with SSG_EPS_SORT=bitonic, the bitonic network (25+ launches)."""
+    if os.environ.get("SSG_EPS_SORT", "sample") == "bitonic" or expect > 2.4e7 or 4.0e5 < expect <= 4.0e6:
+        return "bitonic"
+    return "sample12" if expect > 4.0e6 else "sample10"
+
+
+def _sort_candidates(L, buf, n_cap, n_dev, expect, sort_fail, st):
+    """sort buf[:*n_dev] (capacity n_cap) on the device with the sort `_sort_kind(expect)` names -> the fail word for the check, or None"""
+    kind = _sort_kind(expect)
+    if kind == "bitonic":
+        check(L.ssg_sort_u64_dev(ptr(buf), n_cap, ptr(n_dev), st), "ssg_sort_u64_dev")
+        return None
+    ws_fn, sort_fn, name = ((L.ssg_samplesort_u64_big_workspace_bytes, L.ssg_samplesort_u64_big_dev, "ssg_samplesort_u64_big_dev") if kind == "sample12" else
+                            (L.ssg_samplesort_u64_workspace_bytes, L.ssg_samplesort_u64_dev, "ssg_samplesort_u64_dev"))
+    sws_bytes = int(ws_fn(n_cap))
+    sws = torch.empty(sws_bytes, dtype=torch.uint8, device=buf.device)
+    check(sort_fn(ptr(buf), n_cap, ptr(n_dev), ptr(sws), sws_bytes, ptr(sort_fail), st), name)
+    return sort_fail
+
+
 def _eps_finish(L, h, buf, got, n_pow2, top, st):
     """sort the collected keys, numpy pairwise mean of the first `top` -> (eps, key[top-1] as float64)"""
     dev = h.device
@@ -69,7 +136,7 @@ def _eps_finish(L, h, buf, got, n_pow2, top, st):
 
 
 def _eps_rule_sampled(L, h, rho, st):
-    """Fast path (csrc/cluster.hip "K10, fast path"): sampled float32 threshold, ONE full pass, exactness verified a posteriori.
+    """Fast path (csrc/eps_rule.hip "K10, fast path"): sampled float32 threshold, ONE full pass, exactness verified a posteriori.
     Returns (eps, count, top) or None when the verification fails (the caller then runs the radix select)."""
     dev = h.device
     args = (ptr(h.M), ptr(h.v), h.N, h.row0, h.nrows, h.mode, h.lambda_value)
@@ -93,15 +160,7 @@ def _eps_rule_sampled(L, h, rho, st):
     n_cap = max(2048, 1 << (cap - 1).bit_length())
     buf = torch.empty(n_cap, dtype=torch.int64, device=dev)
     cursor = torch.zeros(3, dtype=torch.int64, device=dev)
-    sp = getattr(h, "sparse", None) if h.mode == 0 else None
-    if sp is not None:
-        # row by row through the sparse copy S of J' where the threshold lies below the row's floor (decided on the device; the dense pass
-        # for the other rows is queued behind it)
-        check(L.ssg_eps_compact_below_s(ptr(h.M), ptr(h.v), h.N, h.row0, h.nrows, h.lambda_value, ptr(thr3), ptr(buf), n_cap, ptr(cursor), ptr(sp["pool"]),
-                                        ptr(sp["seg_off"]), ptr(sp["seg_len"]), sp["nseg"], ptr(sp["cursor"]), ptr(sp["vmin"]), sp["jp0"], ptr(sp["rowmask"]), st),
-              "ssg_eps_compact_below_s")
-    else:
-        check(L.ssg_eps_compact_below(*args, ptr(thr3), ptr(buf), n_cap, ptr(cursor), st), "ssg_eps_compact_below")
+    _compact_below(L, h, thr3, buf, n_cap, cursor, st)
     pend = h.take_pending() if hasattr(h, "take_pending") else None    # the re-rank's status words ride along with this read-back
     npend = int(pend.numel()) if pend is not None else 0
     local = torch.cat([cursor[:2], thr3[:1]] + ([pend.to(torch.int64)] if pend is not None else []))
@@ -160,11 +219,10 @@ def eps_rule(X, rho):
     half matrix (mode 1) -> np.float16 like `tri_mat[:top].mean()` on a float16 array.
     Returns (eps, count, top_num).
     """
-    import os
     L = _lib.lib()
     h = as_handle(X)
     dev, st = h.device, stream()
-    if os.environ.get("SSG_EPS_PATH", "sampled") == "sampled" and float(rho) > 0 and h.N >= 64:
+    if _sampled_path() and float(rho) > 0 and h.N >= 64:
         r = _eps_rule_sampled(L, h, float(rho), st)      # (validates the handle with its first read-back)
         if r is not None:
             return r
@@ -231,30 +289,27 @@ def sparse_row_split(X, rho, eps=None):
     Runs the two passes once more into scratch buffers and reads their row masks (a blocking read each); None without a sparse copy."""
     L = _lib.lib()
     h = as_handle(X)
-    sp = getattr(h, "sparse", None) if h.mode == 0 else None
-    if sp is None:
+    if _sparse(h) is None:
         return None
     h.validate()
-    dev, st, N = h.device, stream(), h.N
+    dev, st = h.device, stream()
     if not h.sparse_complete():
         return {"eps": (0, h.nrows), "region": (0, h.nrows)}
     args = (ptr(h.M), ptr(h.v), h.N, h.row0, h.nrows, h.mode, h.lambda_value)
     z = torch.zeros(2 * 4097 + 5 + 1 + 3 + 2, dtype=torch.int64, device=dev)
     thr3, cursor, ecur = z[8194:8199], z[8200:8203], z[8203:8205]
-    check(L.ssg_eps_sample_threshold(*args, max(1, h.nrows // 192), 1.3 * float(rho), ptr(z[:8194]), ptr(thr3), ptr(z[8199:8200]), None, st), "ssg_eps_sample_threshold")
+    check(L.ssg_eps_sample_threshold(*args, max(1, h.nrows // 192), 1.3 * float(rho), ptr(z[:8194]), ptr(thr3), ptr(z[8199:8200]), st), "ssg_eps_sample_threshold")
     n_cap = 1 << 16
     buf = torch.empty(n_cap, dtype=torch.int64, device=dev)
     mask = torch.zeros(h.nrows, dtype=torch.uint8, device=dev)
-    check(L.ssg_eps_compact_below_s(ptr(h.M), ptr(h.v), h.N, h.row0, h.nrows, h.lambda_value, ptr(thr3), ptr(buf), n_cap, ptr(cursor), ptr(sp["pool"]),
-                                    ptr(sp["seg_off"]), ptr(sp["seg_len"]), sp["nseg"], ptr(sp["cursor"]), ptr(sp["vmin"]), sp["jp0"], ptr(mask), st), "ssg_eps_compact_below_s")
+    _compact_below(L, h, thr3, buf, n_cap, cursor, st, rowmask=mask)
     dense_e = int(mask.ne(0).sum().item())
     out = {"eps": (h.nrows - dense_e, dense_e)}
     if eps is not None:
         cnt = torch.empty(h.nrows, dtype=torch.int32, device=dev)
         edges = torch.empty((1 << 16, 2), dtype=torch.int32, device=dev)
         mask.zero_()
-        check(L.ssg_region_query_s(ptr(h.M), ptr(h.v), N, h.row0, h.nrows, h.lambda_value, float(eps), ptr(sp["pool"]), ptr(sp["seg_off"]), ptr(sp["seg_len"]),
-                                   sp["nseg"], ptr(sp["cursor"]), ptr(sp["vmin"]), sp["jp0"], ptr(mask), ptr(cnt), ptr(edges), 1 << 16, ptr(ecur), st), "ssg_region_query_s")
+        _region_query(L, h, float(eps), cnt, edges, 1 << 16, ecur, st, rowmask=mask)
         dense_r = int(mask.ne(0).sum().item())
         out["region"] = (h.nrows - dense_r, dense_r)
     return out
@@ -284,7 +339,6 @@ def _eps_rule_dbscan_sharded(L, h, rho, min_samples, two_calls):
     Any failed check is seen identically by every rank (all of them decide from the same gathered words) and the two-call form answers."""
     import torch.distributed as dist
     from .dist import gather_packed, shard_bounds
-    import os
     g = h.group
     world, rk = dist.get_world_size(g), dist.get_rank(g)
     dev, st, N = h.device, stream(), h.N
@@ -299,19 +353,13 @@ def _eps_rule_dbscan_sharded(L, h, rho, min_samples, two_calls):
     # the LOCAL quantile is taken wider than the one-GPU chain's 1.3 * rho: a rank whose rows hold more small distances than the average
     # (big identities) would otherwise cut below the global top-th key and fail the check -- 1.6 tolerates a 60 % denser block
     qf = float(os.environ.get("SSG_EPS_SHARD_QUANTILE", "1.6"))
-    check(L.ssg_eps_sample_threshold(*args, stride, qf * rho, ptr(hist1), ptr(thr3), ptr(tick), None, st), "ssg_eps_sample_threshold")
+    check(L.ssg_eps_sample_threshold(*args, stride, qf * rho, ptr(hist1), ptr(thr3), ptr(tick), st), "ssg_eps_sample_threshold")
     # one capacity for every rank (the buffers travel in a flat all-gather): twice the expected candidates of the rank with the largest
     # part of the triangle (rank 0: 15/64 of it on 8 ranks, not 1/8) + a floor
     share = max(_triangle_share(N, *shard_bounds(N, r, world)) for r in range(world))
     n_cap = int(2 * qf * top_guess * share) + (1 << 16)
     buf = torch.empty(n_cap, dtype=torch.int64, device=dev)
-    sp = getattr(h, "sparse", None) if h.mode == 0 else None
-    if sp is not None:
-        check(L.ssg_eps_compact_below_s(ptr(h.M), ptr(h.v), h.N, h.row0, h.nrows, h.lambda_value, ptr(thr3), ptr(buf), n_cap, ptr(cursor), ptr(sp["pool"]),
-                                        ptr(sp["seg_off"]), ptr(sp["seg_len"]), sp["nseg"], ptr(sp["cursor"]), ptr(sp["vmin"]), sp["jp0"], ptr(sp["rowmask"]), st),
-              "ssg_eps_compact_below_s")
-    else:
-        check(L.ssg_eps_compact_below(*args, ptr(thr3), ptr(buf), n_cap, ptr(cursor), st), "ssg_eps_compact_below")
+    _compact_below(L, h, thr3, buf, n_cap, cursor, st)
     # ---- collective 1: candidates + (count, zeros, threshold) of every rank
     g_head, g_buf = gather_packed([torch.cat([cursor[:2], thr3[:1]]), buf], g)          # [world, 3], [world, n_cap] (strided views of the receive buffer)
     cap_all = world * n_cap
@@ -324,19 +372,7 @@ def _eps_rule_dbscan_sharded(L, h, rho, min_samples, two_calls):
     gcur[1:2] = g_head[:, 1].sum()
     thrg[0:1] = g_head[:, 2].min()
     tree = _eps_tree(L, top_guess, dev, st)
-    if os.environ.get("SSG_EPS_SORT", "sample") == "bitonic" or qf * top_guess > 2.4e7 or 4.0e5 < qf * top_guess <= 4.0e6:
-        check(L.ssg_sort_u64_dev(ptr(allk), n_pow2, ptr(ktot), st), "ssg_sort_u64_dev")
-        sf = None
-    elif qf * top_guess > 4.0e6:
-        sws_bytes = int(L.ssg_samplesort_u64_big_workspace_bytes(n_pow2))
-        sws = torch.empty(sws_bytes, dtype=torch.uint8, device=dev)
-        check(L.ssg_samplesort_u64_big_dev(ptr(allk), n_pow2, ptr(ktot), ptr(sws), sws_bytes, ptr(sort_fail), st), "ssg_samplesort_u64_big_dev")
-        sf = sort_fail
-    else:
-        sws_bytes = int(L.ssg_samplesort_u64_workspace_bytes(n_pow2))
-        sws = torch.empty(sws_bytes, dtype=torch.uint8, device=dev)
-        check(L.ssg_samplesort_u64_dev(ptr(allk), n_pow2, ptr(ktot), ptr(sws), sws_bytes, ptr(sort_fail), st), "ssg_samplesort_u64_dev")
-        sf = sort_fail
+    sf = _sort_candidates(L, allk, n_pow2, ktot, qf * top_guess, sort_fail, st)
     check(L.ssg_eps_mean_check(ptr(allk), top_guess, 1 if h.mode == 1 else 0, ptr(tree), tree.numel(), ptr(eps2), ptr(gcur), ptr(thrg), rho, upper_total, cap_all,
                                ptr(status6), ptr(sf), st), "ssg_eps_mean_check")
     # ---- region query of the local rows with eps read from the device
@@ -344,13 +380,7 @@ def _eps_rule_dbscan_sharded(L, h, rho, min_samples, two_calls):
     cnt = torch.zeros(mx_rows, dtype=torch.int32, device=dev)                             # (padded to the longest block: one shape on every rank)
     ecap = max(64 * mx_rows, 1 << 16)
     edges = torch.empty((ecap, 2), dtype=torch.int32, device=dev)
-    if sp is not None:
-        check(L.ssg_region_query_s_dev(ptr(h.M), ptr(h.v), N, h.row0, h.nrows, h.lambda_value, ptr(eps2), ptr(sp["pool"]), ptr(sp["seg_off"]), ptr(sp["seg_len"]),
-                                       sp["nseg"], ptr(sp["cursor"]), ptr(sp["vmin"]), sp["jp0"], ptr(sp["rowmask"]), ptr(cnt), ptr(edges), ecap, ptr(ecur), st),
-              "ssg_region_query_s_dev")
-    else:
-        check(L.ssg_region_query_dev(ptr(h.M), ptr(h.v), N, h.row0, h.nrows, h.mode, h.lambda_value, ptr(eps2), ptr(cnt), ptr(edges), ecap, ptr(ecur), st),
-              "ssg_region_query_dev")
+    _region_query(L, h, eps2, cnt, edges, ecap, ecur, st)
     # ---- collective 2: edge count, neighbour counts, edge list and the re-rank's status words of every rank
     pend = h.take_pending() if hasattr(h, "take_pending") else None
     npend = int(pend.numel()) if pend is not None else 0
@@ -399,7 +429,6 @@ def eps_rule_dbscan(X, rho, min_samples=4):
     What the host decides BEFORE the data is seen, and the device verifies: the number of summands top = round(rho * count) assumes no
     zero entry in the strict upper triangle (count = N(N-1)/2; a zero -- duplicate images -- makes `ssg_eps_check` fail and the
     two-call path runs instead); the sort runs on the device's own candidate count inside a buffer sized by the sampling bound."""
-    import os
     L = _lib.lib()
     h = as_handle(X)
     rho = float(rho)
@@ -414,7 +443,7 @@ def eps_rule_dbscan(X, rho, min_samples=4):
     N = h.N
     upper_total = N * (N - 1) // 2
     top_guess = int(np.round(rho * upper_total))
-    if (os.environ.get("SSG_EPS_PATH", "sampled") != "sampled" or os.environ.get("SSG_EPS_FUSED", "1") == "0" or not rho > 0
+    if (not _sampled_path() or os.environ.get("SSG_EPS_FUSED", "1") == "0" or not rho > 0
             or N < 64 or top_guess <= 0):
         return two_calls()
     if h.group is not None:
@@ -423,90 +452,38 @@ def eps_rule_dbscan(X, rho, min_samples=4):
     args = (ptr(h.M), ptr(h.v), h.N, h.row0, h.nrows, h.mode, h.lambda_value)
     # ---- ONE zero-filled allocation holds every small table of the chain AND everything the host reads at the end (round 6: the read-back
     # needs no concatenation / conversion launches, the components' workspace no initialisation launch of its own), int64 words:
-    #   [hist1 4097 | hist2 4097 | tickets 1 | thr5 5 | cursor 3 | sort_fail 1 | splitters 1024 | bucket counts 1024 || ecur 2 | status6 6 | eps2 2 |
+    #   [hist1 4097 | hist2 4097 | tickets 1 | thr5 5 | cursor 3 | sort_fail 1 || ecur 2 | status6 6 | eps2 2 |
     #    cnt (int32) | ws: parent, lab (int32), ...]
     stride = max(1, h.nrows // 192)
     ws_bytes = int(L.ssg_dbscan_cc_workspace_bytes(N))
     ncnt = (h.nrows + 1) // 2
-    o_small, o_out = 2 * 4097, 2 * 4097 + 10 + 2048
+    o_small, o_out = 2 * 4097, 2 * 4097 + 10
     o_cnt = o_out + 10
     o_ws = o_cnt + ncnt
     z = torch.zeros(o_ws + (ws_bytes + 7) // 8, dtype=torch.int64, device=dev)
     hist = z[:o_small]
     tickets, thr3, cursor, sort_fail = z[o_small:o_small + 1], z[o_small + 1:o_small + 6], z[o_small + 6:o_small + 9], z[o_small + 9:o_small + 10]
-    splitters, gcount = z[o_small + 10:o_small + 1034], z[o_small + 1034:o_small + 2058]
     ecur, status6, eps2 = z[o_out:o_out + 2], z[o_out + 2:o_out + 8], z[o_out + 8:o_out + 10].view(torch.float64)
     cnt = z[o_cnt:o_ws].view(torch.int32)[:h.nrows]
     ws_buf = z[o_ws:].view(torch.uint8)
     # ---- the sampled threshold (two launches: each level's last workgroup selects) and the one full pass
-    fused = os.environ.get("SSG_EPS_FUSED_LAUNCHES", "1") != "0"      # (0: the separate selection / check launches of round 5 -- A/B switch)
-    if fused:
-        # (the interpolated sort splitters are only computed for the rejected SSG_EPS_PRESPLIT experiment: one thread may own hundreds of them,
-        # 33 us in the selecting workgroup -- round 6 measured the chain at 0.39 instead of 0.31 ms while they were always written)
-        presplit = os.environ.get("SSG_EPS_PRESPLIT", "0") == "1"
-        check(L.ssg_eps_sample_threshold(*args, stride, 1.3 * rho, ptr(hist), ptr(thr3), ptr(tickets), ptr(splitters) if presplit else None, st),
-              "ssg_eps_sample_threshold")
-    else:
-        check(L.ssg_eps_sample_hist(*args, stride, None, ptr(hist[:4097]), st), "ssg_eps_sample_hist")
-        check(L.ssg_eps_select_threshold(ptr(hist[:4097]), 1.3 * rho, ptr(thr3), st), "ssg_eps_select_threshold")
-        check(L.ssg_eps_sample_hist(*args, stride, ptr(thr3), ptr(hist[4097:]), st), "ssg_eps_sample_hist")
-        check(L.ssg_eps_refine_threshold(ptr(hist[4097:]), ptr(thr3), st), "ssg_eps_refine_threshold")
+    check(L.ssg_eps_sample_threshold(*args, stride, 1.3 * rho, ptr(hist), ptr(thr3), ptr(tickets), st), "ssg_eps_sample_threshold")
     # the threshold sits at the 1.3 * rho quantile of ~3 M sampled entries (about 1 % sampling error on the count below it): twice the
     # expected top + a floor holds the candidates with a wide margin -- and keeps the launched sort network two levels shorter than the
     # two-call path's 6x bound (a fuller buffer fails the check and the two-call path answers)
     cap = max(2 * top_guess * h.nrows // N + (1 << 16), 1 << 16)
     n_cap = max(2048, 1 << (cap - 1).bit_length())
     buf = torch.empty(n_cap, dtype=torch.int64, device=dev)
-    sp = getattr(h, "sparse", None) if h.mode == 0 else None
-    if sp is not None:
-        check(L.ssg_eps_compact_below_s(ptr(h.M), ptr(h.v), h.N, h.row0, h.nrows, h.lambda_value, ptr(thr3), ptr(buf), n_cap, ptr(cursor), ptr(sp["pool"]),
-                                        ptr(sp["seg_off"]), ptr(sp["seg_len"]), sp["nseg"], ptr(sp["cursor"]), ptr(sp["vmin"]), sp["jp0"], ptr(sp["rowmask"]), st),
-              "ssg_eps_compact_below_s")
-    else:
-        check(L.ssg_eps_compact_below(*args, ptr(thr3), ptr(buf), n_cap, ptr(cursor), st), "ssg_eps_compact_below")
+    _compact_below(L, h, thr3, buf, n_cap, cursor, st)
     # ---- sort (device-sized), numpy's pairwise mean of the first top_guess keys + the checks in the tree kernel -- no read-back
     tree = _eps_tree(L, top_guess, dev, st)
-    # sample sort (4 launches) while its 1024 sorting buckets stay LDS-sized: ~1.3 * top candidates expected, a bucket may run to 4x the
-    # mean, 2048 keys fit -> up to 4e5 candidates (N = 16 000: 2.7e5); above that the bitonic network (25+ launches) as in round 4
-    expect = 1.3 * top_guess * h.nrows / N
-    if os.environ.get("SSG_EPS_SORT", "sample") == "bitonic" or expect > 2.4e7 or 4.0e5 < expect <= 4.0e6:
-        check(L.ssg_sort_u64_dev(ptr(buf), n_cap, ptr(cursor), st), "ssg_sort_u64_dev")
-        sf = None
-    elif expect > 4.0e6:
-        # round 6: 4095 splitters, buckets of up to 16 384 keys sorted in 128 KB of LDS (N = 128 000: 1.7e7 candidates: 3.0 ms against 6.9 of the
-        # network; measured slower than the network below ~4e6 keys -- tools/time_sort.py -- so N = 30 000's 9.4e5 candidates keep the network)
-        sws_bytes = int(L.ssg_samplesort_u64_big_workspace_bytes(n_cap))
-        sws = torch.empty(sws_bytes, dtype=torch.uint8, device=dev)
-        check(L.ssg_samplesort_u64_big_dev(ptr(buf), n_cap, ptr(cursor), ptr(sws), sws_bytes, ptr(sort_fail), st), "ssg_samplesort_u64_big_dev")
-        sf = sort_fail
-    else:
-        sws_bytes = int(L.ssg_samplesort_u64_workspace_bytes(n_cap))
-        sws = torch.empty(sws_bytes, dtype=torch.uint8, device=dev)
-        if fused and os.environ.get("SSG_EPS_PRESPLIT", "0") == "1":
-            # (opt-in, measured and rejected: splitters interpolated in the sample histogram save the 37 us sample sort, but final_dist takes
-            # few distinct values -- half J' plus a half source term -- and thousands of EQUAL keys then share one sorting bucket: the
-            # sorted sample gives such a value a bucket of its own, an interpolated splitter cannot.  20 ms instead of 0.33 at N = 16 000.)
-            check(L.ssg_samplesort_u64_presplit_dev(ptr(buf), n_cap, ptr(cursor), ptr(splitters), ptr(gcount), ptr(sws), sws_bytes, ptr(sort_fail), st),
-                  "ssg_samplesort_u64_presplit_dev")
-        else:
-            check(L.ssg_samplesort_u64_dev(ptr(buf), n_cap, ptr(cursor), ptr(sws), sws_bytes, ptr(sort_fail), st), "ssg_samplesort_u64_dev")
-        sf = sort_fail
-    if fused:
-        check(L.ssg_eps_mean_check(ptr(buf), top_guess, 1 if h.mode == 1 else 0, ptr(tree), tree.numel(), ptr(eps2), ptr(cursor), ptr(thr3), rho, upper_total, n_cap,
-                                   ptr(status6), ptr(sf), st), "ssg_eps_mean_check")
-    else:
-        check(L.ssg_eps_mean_run(ptr(buf), top_guess, 1 if h.mode == 1 else 0, ptr(tree), tree.numel(), ptr(eps2), st), "ssg_eps_mean_run")
-        check(L.ssg_eps_check(ptr(buf), ptr(cursor), ptr(thr3), rho, upper_total, top_guess, n_cap, ptr(eps2), ptr(status6), ptr(sf), st), "ssg_eps_check")
+    sf = _sort_candidates(L, buf, n_cap, cursor, 1.3 * top_guess * h.nrows / N, sort_fail, st)      # (~1.3 * top candidates expected)
+    check(L.ssg_eps_mean_check(ptr(buf), top_guess, 1 if h.mode == 1 else 0, ptr(tree), tree.numel(), ptr(eps2), ptr(cursor), ptr(thr3), rho, upper_total, n_cap,
+                               ptr(status6), ptr(sf), st), "ssg_eps_mean_check")
     # ---- region query with eps read from the device, components; the labels stay int32 in the workspace (0x7fffffff = noise)
     ecap = max(64 * h.nrows, 1 << 16)
     edges = torch.empty((ecap, 2), dtype=torch.int32, device=dev)
-    if sp is not None:
-        check(L.ssg_region_query_s_dev(ptr(h.M), ptr(h.v), N, h.row0, h.nrows, h.lambda_value, ptr(eps2), ptr(sp["pool"]), ptr(sp["seg_off"]), ptr(sp["seg_len"]),
-                                       sp["nseg"], ptr(sp["cursor"]), ptr(sp["vmin"]), sp["jp0"], ptr(sp["rowmask"]), ptr(cnt), ptr(edges), ecap, ptr(ecur), st),
-              "ssg_region_query_s_dev")
-    else:
-        check(L.ssg_region_query_dev(ptr(h.M), ptr(h.v), N, h.row0, h.nrows, h.mode, h.lambda_value, ptr(eps2), ptr(cnt), ptr(edges), ecap, ptr(ecur), st),
-              "ssg_region_query_dev")
+    _region_query(L, h, eps2, cnt, edges, ecap, ecur, st)
     check(L.ssg_dbscan_cc_dev(ptr(cnt), ptr(edges), ptr(ecur), ecap, N, int(min_samples), ptr(ws_buf), ws_bytes, None, st), "ssg_dbscan_cc_dev")
     # ---- THE read: the contiguous tail of `z` up to the end of the int32 labels, and the re-rank's raw status words, as DMA copies into one
     # page-locked buffer behind the chain -- no concatenation launch -- and one wait
@@ -587,18 +564,9 @@ class DBSCAN:
             h.validate()
         while True:
             edges = torch.empty((cap, 2), dtype=torch.int32, device=dev)
-            cursor = torch.zeros(1, dtype=torch.int64, device=dev)
-            sp = getattr(h, "sparse", None) if h.mode == 0 else None
-            if sp is not None:
-                # row by row through the sparse copy S of J' where eps lies below the row's floor (decided on the device), dense scan of the rest
-                cursor = torch.zeros(2, dtype=torch.int64, device=dev)
-                check(L.ssg_region_query_s(ptr(h.M), ptr(h.v), N, h.row0, h.nrows, h.lambda_value, eps, ptr(sp["pool"]), ptr(sp["seg_off"]), ptr(sp["seg_len"]),
-                                           sp["nseg"], ptr(sp["cursor"]), ptr(sp["vmin"]), sp["jp0"], ptr(sp["rowmask"]), ptr(cnt), ptr(edges), cap, ptr(cursor), st),
-                      "ssg_region_query_s")
-                cursor = cursor[:1]
-            else:
-                check(L.ssg_region_query(ptr(h.M), ptr(h.v), N, h.row0, h.nrows, h.mode, h.lambda_value, eps, ptr(cnt), ptr(edges), cap,
-                                         ptr(cursor), st), "ssg_region_query")
+            cursor2 = torch.zeros(2, dtype=torch.int64, device=dev)
+            _region_query(L, h, eps, cnt, edges, cap, cursor2, st)
+            cursor = cursor2[:1]
             if h.group is None:
                 # one GPU: components and labels follow on the stream, the edge count stays on the device; ONE read-back at
                 # the end brings labels, neighbour counts and the count (which tells whether the edge list was big enough)

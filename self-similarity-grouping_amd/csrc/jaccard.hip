@@ -257,7 +257,7 @@ __global__ __launch_bounds__(64) void jaccard_rows_kernel(const int32_t* __restr
 //   * the touched entries also go out as a SPARSE copy S of the row: packed (J' << 17 | column) words in a pool, one segment per
 //     (row, column chunk).  Everything not in S equals the constant J'(0) = half(1 - lambda), the largest value a row holds; the
 //     eps rule and the region query only ever ask for entries BELOW a bound, so while that bound stays under J'(0) they walk S
-//     (a few hundred entries per row) instead of streaming the N columns again (cluster.hip);
+//     (a few hundred entries per row) instead of streaming the N columns again (eps_rule.hip, dbscan.hip);
 //   * no store drain between rows, and the next row's list heads are fetched before the epilogue of the current one, so that a
 //     wave's rows overlap (the first generation paid the q_nnz -> metadata -> entries load chain at the start of every row).
 struct SparseOut {

@@ -1,7 +1,7 @@
 """Independent reference for the grouping step -- the eps rule and DBSCAN of selftraining.py:289-306 -- at sizes the oracle cannot
 hold (N = 30 000 and 128 000: 7.2 GB and 131 GB of float64).
 
-It shares no code with csrc/cluster.hip.  final_dist is rebuilt row block by row block from the handle's J' and v with plain torch
+It shares no code with csrc/eps_rule.hip and csrc/dbscan.hip.  final_dist is rebuilt row block by row block from the handle's J' and v with plain torch
 element-wise ops (on the device, so that N = 128 000 needs no 32 GB host copy).  The eps rule takes numpy's mean of the sorted exact
 candidate set.  The labels come from sklearn's own DBSCAN on the sparse neighbour graph.  Everything here is exact: a consumer
 compares with `==`, never within a tolerance.

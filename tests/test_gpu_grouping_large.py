@@ -22,8 +22,8 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 import grouping_ref as gr  # noqa: E402
 
-SWITCHES = [{}, {"SSG_EPS_PATH": "radix"}, {"SSG_EPS_FUSED": "0"}, {"SSG_EPS_FUSED_LAUNCHES": "0"}, {"SSG_EPS_SORT": "bitonic"}]
-SWITCH_IDS = ["default", "radix", "unfused", "separate_launches", "bitonic"]
+SWITCHES = [{}, {"SSG_EPS_PATH": "radix"}, {"SSG_EPS_FUSED": "0"}, {"SSG_EPS_SORT": "bitonic"}]
+SWITCH_IDS = ["default", "radix", "unfused", "bitonic"]
 
 
 @pytest.fixture(scope="module")

@@ -319,13 +319,9 @@ def test_fused_sampling_and_check_launches_equal_the_separate_ones(dev):
         assert np.isfinite(np.uint32(ref_thr[0]).view(np.float32)) and ref_thr[1] > 1000
         for rep in range(30):
             junk = torch.randn(1 << 20, device=dev).sin_()                              # (other work in flight on the stream)
-            z = torch.zeros(2 * 4097 + 5 + 1 + 1024, dtype=torch.int64, device=dev)
-            check(L.ssg_eps_sample_threshold(*args, stride, 1.3 * rho, ptr(z[:8194]), ptr(z[8194:8199]), ptr(z[8199:8200]), ptr(z[8200:]), stream()), "fused")
+            z = torch.zeros(2 * 4097 + 5 + 1, dtype=torch.int64, device=dev)
+            check(L.ssg_eps_sample_threshold(*args, stride, 1.3 * rho, ptr(z[:8194]), ptr(z[8194:8199]), ptr(z[8199:8200]), stream()), "fused")
             got = z.cpu().numpy()
-            # the splitters derived from the histogram: ascending float64 bit patterns below the (coarse) threshold
-            sp_ = got[8200:8200 + 1023].view(np.uint64)
-            fin = sp_[sp_ != np.uint64(0xFFFFFFFFFFFFFFFF)].view(np.float64)
-            assert len(fin) > 900 and np.all(np.diff(fin) >= 0) and fin[0] > 0 and fin[-1] <= float(np.uint32(ref_thr[0]).view(np.float32)) * 1.01, rep
             assert np.array_equal(got[:8194], ref_hist), rep
             assert np.array_equal(got[8194:8199], ref_thr), (rep, got[8194:8199], ref_thr)
             assert got[8199] == (int(got[8199]) & 0xffffffff) + ((int(got[8199]) >> 32) << 32) and (int(got[8199]) & 0xffffffff) == (int(got[8199]) >> 32) > 0   # both tickets = the grid size

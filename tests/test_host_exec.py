@@ -42,17 +42,17 @@ def hx(tmp_path_factory):
     text = [cut("gram_i8.hip", "__device__ __forceinline__ long long half_units24", stop="halfwave_max"),
             cut("jaccard.hip", "__device__ __forceinline__ hbits jaccard_scaled"),
             cut("krecip.hip", "__device__ float pairwise_sum_f32"),
-            "template <typename T>\n" + cut("cluster.hip", "__device__ T pw_leaf"),
-            cut("cluster.hip", "__device__ __forceinline__ int sur_bin(float x)"),
-            cut("cluster.hip", "__device__ __forceinline__ float sur_bin_upper"),
+            "template <typename T>\n" + cut("eps_rule.hip", "__device__ T pw_leaf"),
+            cut("eps_rule.hip", "__device__ __forceinline__ int sur_bin(float x)"),
+            cut("eps_rule.hip", "__device__ __forceinline__ float sur_bin_upper"),
             cut("topk_intro.hip", "constexpr uint32_t KEY_NAN"),
             cut("topk_intro.hip", "__device__ __forceinline__ uint32_t norm_key"),
-            "template <int NSLOT>\n" + cut("cluster.hip", "__device__ __forceinline__ int ss_bucket")]
+            "template <int NSLOT>\n" + cut("sort_u64.hip", "__device__ __forceinline__ int ss_bucket")]
     assert "sqrt_units48_to_half" in text[0]
     (d / "rules_cut.inc").write_text("\n".join(text))
     (d / "preprocess_cut.inc").write_text(cut("preprocess.hip", "__global__ __launch_bounds__(256) void resize_h_u8_kernel") + "\n" +
                                           cut("preprocess.hip", "__global__ __launch_bounds__(256) void resize_v_normalize_kernel"))
-    (d / "cc_cut.inc").write_text(cut("cluster.hip", "// ------------------------------------------------------------------ K12 union-find", stop="}  // namespace ssg"))
+    (d / "cc_cut.inc").write_text(cut("dbscan.hip", "// ------------------------------------------------------------------ K12 union-find", stop="}  // namespace ssg"))
     (d / "split_cut.inc").write_text(cut("conv.hip", "__device__ __forceinline__ unsigned pack_h2", stop="struct ConvParams"))
     (d / "pool_cut.inc").write_text(cut("conv.hip", "__device__ __forceinline__ void h8l8_load8", stop="// out = (a + b) / ||a + b||_2 per row"))
     so = str(d / "libhx.so")
@@ -220,7 +220,7 @@ def test_rank_key_and_surrogate_bins(hx):
 
 
 def test_sample_sort_bucket_rule(hx):
-    """`ss_bucket` of the device-sized sample sort (cluster.hip, round 5), its own text on the host: bucket = 2 * #(splitters < key) + (key equals
+    """`ss_bucket` of the device-sized sample sort (sort_u64.hip, round 5), its own text on the host: bucket = 2 * #(splitters < key) + (key equals
     that splitter) against numpy's searchsorted, on splitter tables with duplicates -- and the property the sort rests on: the bucket
     number never decreases with the key, and an odd bucket holds copies of ONE key only"""
     rng = np.random.default_rng(21)
@@ -264,7 +264,7 @@ def test_resize_kernels_on_host_match_pillow(hx):
 
 
 def test_union_find_kernels_on_host_number_labels_like_sklearn(hx):
-    """The connected-components kernels of cluster.hip (union-find with path halving, roots = smallest core index, clusters numbered
+    """The connected-components kernels of dbscan.hip (union-find with path halving, roots = smallest core index, clusters numbered
     by an exclusive scan over the roots, border points to the smallest adjacent cluster) executed on the host in ssg_dbscan_cc's launch
     order == sklearn.cluster.DBSCAN(metric='precomputed').fit_predict (selftraining.py:299-306) incl. its numbering, whatever the
     order of the edge list -- blobs with noise, border points shared by two clusters, min_samples 1..6, no edges at all."""

@@ -57,6 +57,30 @@ def test_device_backed_array_never_inherits_its_handle():
     assert a.valid_handle() is None
 
 
+def test_sort_kind_pins_the_candidate_sort_thresholds(monkeypatch):
+    """cluster._sort_kind, the one place where the one-GPU and the sharded eps chain choose the sort of their candidates: the table at its
+    edges (<= 4.0e5 sample sort with 1023 splitters, <= 4.0e6 bitonic network, <= 2.4e7 sample sort with 4095 splitters, beyond: the
+    network), SSG_EPS_SORT=bitonic forcing the network, and at every edge the answer of the condition both chains carried before."""
+    from ssg_amd import cluster
+
+    def before(expect, env):       # the if / elif / else of eps_rule_dbscan and _eps_rule_dbscan_sharded, as they stood
+        if env == "bitonic" or expect > 2.4e7 or 4.0e5 < expect <= 4.0e6:
+            return "bitonic"
+        elif expect > 4.0e6:
+            return "sample12"
+        return "sample10"
+
+    table = [(4.0e5, "sample10"), (4.0e5 + 1, "bitonic"), (4.0e6, "bitonic"), (4.0e6 + 1, "sample12"), (2.4e7, "sample12"), (2.4e7 + 1, "bitonic")]
+    monkeypatch.delenv("SSG_EPS_SORT", raising=False)
+    for expect, kind in table:
+        assert cluster._sort_kind(expect) == kind == before(expect, "sample"), expect
+    monkeypatch.setenv("SSG_EPS_SORT", "bitonic")
+    for expect, _ in table:
+        assert cluster._sort_kind(expect) == "bitonic" == before(expect, "bitonic"), expect
+    monkeypatch.setenv("SSG_EPS_SORT", "sample")
+    assert [cluster._sort_kind(e) for e, _ in table] == [k for _, k in table]
+
+
 def test_resnet_pretrained_and_state_dict_diagnostics():
     """pretrained=True without weights and strict=False loads that match nothing must not be silent."""
     import ssg_amd

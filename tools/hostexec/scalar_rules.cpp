@@ -1,7 +1,7 @@
 // The scalar numerics rules of the device code, executed on the host: csrc/ssg_common.h (half arithmetic as numpy does it, the one-rounding
 // double -> half, final_dist from its compact form) and the scalar helpers of the kernels -- the integer half(sqrt(.)) rounding of
-// gram_i8.hip, jaccard_scaled (jaccard.hip), numpy's pairwise summation (krecip.hip float32, cluster.hip float64 leaves), the rank key of
-// the introsort replay (topk_intro.hip), the eps rule's surrogate bins (cluster.hip) -- are plain scalar C++ behind `__device__`.  The test
+// gram_i8.hip, jaccard_scaled (jaccard.hip), numpy's pairwise summation (krecip.hip float32, eps_rule.hip float64 leaves), the rank key of
+// the introsort replay (topk_intro.hip), the eps rule's surrogate bins (eps_rule.hip) -- are plain scalar C++ behind `__device__`.  The test
 // cuts their text out of the .hip files into rules_cut.inc; with `__device__` mapped to host functions the SAME TEXT is compiled for x86 and
 // compared with numpy on millions of inputs (tests/test_host_exec.py) -- a CPU-side pin of the rules DESIGN.md §4 lists, next to the
 // `-m gpu` tests that run them on the GPU.  Test infrastructure: nothing here is linked into the product.
@@ -82,7 +82,7 @@ float hx_pw_leaf_f32(const unsigned long long* keys, long long off, int n) { ret
 void hx_norm_key(const uint32_t* raw, float fmx, long n, uint32_t* out) { for (long i = 0; i < n; i++) out[i] = norm_key(raw[i], fmx); }
 void hx_sur_bin(const float* x, long n, int* out) { for (long i = 0; i < n; i++) out[i] = sur_bin(x[i]); }
 float hx_sur_bin_upper(int b) { return sur_bin_upper(b); }
-// bucket rule of the device-sized sample sort (cluster.hip ss_bucket): table = 1023 ascending splitters + ~0
+// bucket rule of the device-sized sample sort (sort_u64.hip ss_bucket): table = 1023 ascending splitters + ~0
 void hx_ss_bucket(const unsigned long long* table, const unsigned long long* keys, long n, int* out) { for (long i = 0; i < n; i++) out[i] = ss_bucket<1024>(table, keys[i]); }
 // the two resize kernels of preprocess.hip (grid-stride, one thread here): uint8 [B,h,w,3] -> float32 [B,3,H,W]
 void hx_preprocess(const uint8_t* src, int B, int h, int w, int H, int W, const int32_t* xmin, const int32_t* xcnt, const int32_t* kkx, int ksx,
@@ -90,7 +90,7 @@ void hx_preprocess(const uint8_t* src, int B, int h, int w, int H, int W, const 
   resize_h_u8_kernel(src, tmp, B, h, w, W, xmin, xcnt, kkx, ksx);
   resize_v_normalize_kernel(tmp, out, B, h, H, W, ymin, ycnt, kky, ksy, m[0], m[1], m[2], sd[0], sd[1], sd[2]);
 }
-// ssg_dbscan_cc's launch sequence (cluster.hip dbscan_cc_impl) with the kernels' own text: per-index kernels run index by index, the
+// ssg_dbscan_cc's launch sequence (dbscan.hip dbscan_cc_impl) with the kernels' own text: per-index kernels run index by index, the
 // grid-stride ones (union, border) as one thread over the edge list in the order given; the exclusive scan of the root flags (a wave-level
 // kernel on the device) is restated here
 void hx_dbscan_cc(const int32_t* cnt, const int32_t* edges, unsigned long long ne, int N, int min_samples, int64_t* labels) {

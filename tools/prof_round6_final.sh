@@ -44,5 +44,5 @@ if has micro; then
   timeout 600 python tools/ab_inproc.py --reps 8 base=self-similarity-grouping_amd/libssg_hip.so wm128=self-similarity-grouping_amd/libssg_hip.so,SSG_CONV_TALL_WM=128 wm128x2=self-similarity-grouping_amd/libssg_hip.so,SSG_CONV_TALL_WM=129 > $O/ab_conv_wm.txt 2>&1; tail -4 $O/ab_conv_wm.txt
   (SSG_TC_NOCAND=1 timeout 300 python tools/time_compact.py 16000 30000 64000 2>&1 | grep "N=") > $O/dense_passes.txt; cat $O/dense_passes.txt
   (timeout 300 python tools/time_sort.py 270000 940000 4000000 17000000 2>&1 | grep "n=") > $O/sorts.txt; cat $O/sorts.txt
-  (for k in 1 0; do SSG_EPS_FUSED_LAUNCHES=$k timeout 200 python tools/time_eps_chain.py 2>&1 | tail -1 | sed "s/^/SSG_EPS_FUSED_LAUNCHES=$k: /"; done) > $O/eps_chain_timing.txt; cat $O/eps_chain_timing.txt
+  (timeout 200 python tools/time_eps_chain.py 2>&1 | tail -1) > $O/eps_chain_timing.txt; cat $O/eps_chain_timing.txt
 fi

@@ -19,7 +19,7 @@ for N in [int(a) for a in sys.argv[1:]] or [30000]:
     args = (ptr(h.M), ptr(h.v), h.N, h.row0, h.nrows, h.mode, h.lambda_value)
     rho = 1.6e-3
     z = torch.zeros(2 * 4097 + 5 + 1, dtype=torch.int64, device=dev)
-    check(L.ssg_eps_sample_threshold(*args, max(1, N // 192), 1.3 * rho, ptr(z[:8194]), ptr(z[8194:8199]), ptr(z[8199:]), None, stream()), "thr")
+    check(L.ssg_eps_sample_threshold(*args, max(1, N // 192), 1.3 * rho, ptr(z[:8194]), ptr(z[8194:8199]), ptr(z[8199:]), stream()), "thr")
     thr3 = z[8194:8199]
     top = int(np.round(rho * (N * (N - 1) // 2)))
     n_cap = 1 << (2 * top + (1 << 16) - 1).bit_length()

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""The three device-sized sorts of the eps rule on n keys inside a 2^k capacity (development aid): bitonic network, sample sort (LB = 10)
-and the big sample sort (LB = 12).  usage: time_sort.py n [n ...]"""
+"""The three device-sized sorts of the eps rule on n keys inside a 2^k capacity (development aid): bitonic network (count on the device, and
+on the host), sample sort (LB = 10) and the big sample sort (LB = 12).  usage: time_sort.py n [n ...]"""
 import os, sys
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -25,6 +25,11 @@ for n in [int(a) for a in sys.argv[1:]] or [270000, 940000, 17000000]:
         return min(ts), ok
     fail = torch.zeros(1, dtype=torch.int64, device=dev)
     out = {"bitonic": timed(lambda b: check(L.ssg_sort_u64_dev(ptr(b), n_cap, ptr(nd), stream()), "s"))}
+    # the same network with the count on the host (the two-call path): fill [n, n_pow2), sort n_pow2 = the length the device-count form works on
+    n_pow2 = max(2048, 1 << (n - 1).bit_length())
+    def host_count(b):
+        check(L.ssg_fill_u64(ptr(b), n, n_pow2, 0xFFFFFFFFFFFFFFFF, stream()), "f"); check(L.ssg_sort_u64(ptr(b), n_pow2, stream()), "s")
+    out["bitonic_host"] = timed(host_count)
     w10 = torch.empty(int(L.ssg_samplesort_u64_workspace_bytes(n_cap)), dtype=torch.uint8, device=dev)
     if n <= 3000000:
         out["sample10"] = timed(lambda b: check(L.ssg_samplesort_u64_dev(ptr(b), n_cap, ptr(nd), ptr(w10), w10.numel(), ptr(fail), stream()), "s"))
