@@ -131,7 +131,11 @@ int ssg_krecip(const uint16_t* D, const uint32_t* rowmax, const int32_t* rank, i
  * max(v_nnz) read back, or a GUESS); q_* cover rows [row0,row0+nrows) with row stride capQ >= k2*max_nnz.
  * overflow (device int32 [2], zeroed by the caller, may be NULL; round 4): [0] = the longest V row met when one exceeds max_nnz (that
  * row of q_* is then truncated, never written out of bounds), [1] = the longest V row met at all -- lets the caller run on a guessed
- * max_nnz without a host round trip, redo the rare miss and size its next guess. */
+ * max_nnz without a host round trip, redo the rare miss and size its next guess.
+ * One wave stages the min(k2, N, K) V rows of a row in LDS (about 10 bytes per entry of max_nnz each): the call runs 4, 2 or 1 rows per
+ * workgroup, whatever fits 160 KB -- ssg_query_expand_rows_per_group tells which, 0 when one row alone does not fit (k2 = 64 fits rows
+ * of up to 255 entries); the call then returns SSG_ERR_INVALID. */
+int ssg_query_expand_rows_per_group(int N, int K, int k2, int max_nnz);
 int ssg_query_expand(const int32_t* v_idx, const uint16_t* v_val, const int32_t* v_nnz, const int32_t* rank, int N, int row0, int nrows,
                      int K, int k2, int capV, int capQ, int max_nnz, int32_t* q_idx, uint16_t* q_val, int32_t* q_nnz, int32_t* overflow,
                      ssg_stream_t stream);

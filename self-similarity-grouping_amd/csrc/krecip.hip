@@ -206,18 +206,21 @@ __device__ __forceinline__ int lower_bound_i32(const int32_t* a, int n, int x) {
   return lo;
 }
 
-// LDS per wave: for each of k2 lists: idx[capV] int32 | val[capV] half | hpre[capV+1] int32
-__global__ __launch_bounds__(256) void query_expand_kernel(const int32_t* __restrict__ v_idx, const hbits* __restrict__ v_val,
+// LDS per wave: for each of k2 lists: idx[capL] int32 | hpre[capL+1] int32 | val[capL] half; then the k2 list lengths (NN_BYTES: 64 holds
+// up to 16 lists -- the layout every call had before k2 > 16 was supported, kept for them instruction for instruction -- 256 holds 64).
+// WAVES rows per workgroup: 4, or fewer when k2 staged rows of capL entries would not fit four times into the LDS.
+template <int WAVES, int NN_BYTES>
+__global__ __launch_bounds__(WAVES * 64) void query_expand_kernel(const int32_t* __restrict__ v_idx, const hbits* __restrict__ v_val,
                                                            const int32_t* __restrict__ v_nnz, const int32_t* __restrict__ rank,
                                                            int row0, int nrows, int K, int kk, int capV, int capQ, int capL,
                                                            int32_t* __restrict__ q_idx, hbits* __restrict__ q_val,
                                                            int32_t* __restrict__ q_nnz, int32_t* __restrict__ overflow) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int wave = (int)(threadIdx.x >> 6), lane = lane_id();
-  const int il = (int)blockIdx.x * 4 + wave;
+  const int il = (int)blockIdx.x * WAVES + wave;
   // capL = longest source row actually present (LDS is sized for it, not for the worst-case capV)
   const size_t per_list = (size_t)capL * 4 + (size_t)(capL + 1) * 4 + (((size_t)capL * 2 + 3) & ~(size_t)3);
-  const size_t per_wave = (per_list * kk + 64 + 15) & ~(size_t)15;
+  const size_t per_wave = (per_list * kk + NN_BYTES + 15) & ~(size_t)15;
   unsigned char* wbase = smem + (size_t)wave * per_wave;
   if (il >= nrows) return;
   const int i = row0 + il;
@@ -348,6 +351,24 @@ extern "C" int ssg_krecip(const uint16_t* D, const uint32_t* rowmax, const int32
   return SSG_OK;
 }
 
+// LDS of the query expansion, as query_expand_kernel lays it out: the list lengths take 64 bytes up to 16 lists, 256 above
+static inline int qe_nn_bytes(int kk) { return kk <= 16 ? 64 : 256; }
+static inline size_t qe_wave_bytes(int kk, int capL) {
+  const size_t per_list = (size_t)capL * 4 + (size_t)(capL + 1) * 4 + (((size_t)capL * 2 + 3) & ~(size_t)3);
+  return (per_list * kk + qe_nn_bytes(kk) + 15) & ~(size_t)15;
+}
+
+// rows (waves) per workgroup ssg_query_expand runs with: the most of 4, 2, 1 whose staged lists fit 160 KB of LDS; 0 = one row alone
+// does not fit (the call is refused)
+extern "C" int ssg_query_expand_rows_per_group(int N, int K, int k2, int max_nnz) {
+  int kk = k2; if (kk > N) kk = N; if (kk > K) kk = K;
+  if (kk <= 0) return 0;
+  const size_t per_wave = qe_wave_bytes(kk, max_nnz < 1 ? 1 : max_nnz);
+  for (int waves = 4; waves >= 1; waves >>= 1)
+    if (per_wave * waves <= 160 * 1024) return waves;
+  return 0;
+}
+
 extern "C" int ssg_query_expand(const int32_t* v_idx, const uint16_t* v_val, const int32_t* v_nnz, const int32_t* rank, int N, int row0,
                                 int nrows, int K, int k2, int capV, int capQ, int max_nnz, int32_t* q_idx, uint16_t* q_val, int32_t* q_nnz,
                                 int32_t* overflow, hipStream_t stream) {
@@ -357,13 +378,23 @@ extern "C" int ssg_query_expand(const int32_t* v_idx, const uint16_t* v_val, con
     ssg_set_error("ssg_query_expand: need max_nnz (%d) <= capV (%d) and capQ (%d) >= k2*max_nnz (%d)", max_nnz, capV, capQ, kk * capL);
     return SSG_ERR_INVALID;
   }
-  const size_t per_list = (size_t)capL * 4 + (size_t)(capL + 1) * 4 + (((size_t)capL * 2 + 3) & ~(size_t)3);
-  const size_t per_wave = (per_list * kk + 64 + 15) & ~(size_t)15;
-  const size_t lds = per_wave * 4;
-  if (lds > 160 * 1024) { ssg_set_error("ssg_query_expand: k2=%d max_nnz=%d needs %zu B LDS", k2, capL, lds); return SSG_ERR_INVALID; }
-  if (lds > 64 * 1024) SSG_HIP(hipFuncSetAttribute((const void*)query_expand_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(query_expand_kernel, dim3((nrows + 3) / 4), dim3(256), lds, stream, v_idx, v_val, v_nnz, rank, row0, nrows, K, kk, capV,
-                     capQ, capL, q_idx, q_val, q_nnz, overflow);
+  const int nn_bytes = qe_nn_bytes(kk);
+  const size_t per_wave = qe_wave_bytes(kk, capL);
+  const int waves = ssg_query_expand_rows_per_group(N, K, k2, max_nnz);
+  if (waves == 0) { ssg_set_error("ssg_query_expand: k2=%d max_nnz=%d needs %zu B LDS for one row", k2, capL, per_wave); return SSG_ERR_INVALID; }
+  const size_t lds = per_wave * waves;
+#define SSG_QE_LAUNCH(W, B)                                                                                                                      \
+  {                                                                                                                                              \
+    if (lds > 64 * 1024) SSG_HIP(hipFuncSetAttribute((const void*)query_expand_kernel<W, B>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
+    hipLaunchKernelGGL((query_expand_kernel<W, B>), dim3((nrows + W - 1) / W), dim3(W * 64), lds, stream, v_idx, v_val, v_nnz, rank, row0, nrows, K, kk, \
+                       capV, capQ, capL, q_idx, q_val, q_nnz, overflow);                                                                        \
+  }
+  if (nn_bytes == 64) {
+    if (waves == 4) SSG_QE_LAUNCH(4, 64) else if (waves == 2) SSG_QE_LAUNCH(2, 64) else SSG_QE_LAUNCH(1, 64)
+  } else {
+    if (waves == 4) SSG_QE_LAUNCH(4, 256) else if (waves == 2) SSG_QE_LAUNCH(2, 256) else SSG_QE_LAUNCH(1, 256)
+  }
+#undef SSG_QE_LAUNCH
   SSG_LAUNCH_CHECK("query_expand_kernel");
   return SSG_OK;
 }

@@ -367,6 +367,7 @@ def re_ranking_device(src, tgt, k1=20, k2=6, lambda_value=0.2, no_rerank=False, 
     if N < 2:
         raise ValueError("re_ranking needs at least 2 target samples")
     if not no_rerank and (k1 < 1 or k2 < 1 or max(k1 + 1, k2) > 64):
+        # (inside this range one more limit depends on the data: the query expansion stages k2 k-reciprocal rows in LDS, see `tail`)
         raise ValueError("re_ranking on the GPU supports 1 <= k1 <= 63 and 1 <= k2 <= 64 (got k1=%r, k2=%r)" % (k1, k2))
     src = _as_dev_f32(src, dev); tgt = _as_dev_f32(tgt, dev)
     d = tgt.shape[1]
@@ -457,11 +458,18 @@ def re_ranking_device(src, tgt, k1=20, k2=6, lambda_value=0.2, no_rerank=False, 
                           seg_off=torch.empty(nrows * nseg, dtype=torch.int64, device=dev), seg_len=torch.empty(nrows * nseg, dtype=torch.int32, device=dev),
                           nseg=nseg, jp0=int(om), vmin=torch.empty(1, dtype=torch.int32, device=dev), rowmask=torch.empty(nrows, dtype=torch.uint8, device=dev))
 
+        def qe_fits(mx):
+            return int(L.ssg_query_expand_rows_per_group(N, K, k2, mx)) != 0
+
         def tail(mx, over):
             """local query expansion -> inverted index -> Jaccard rows into Jp, with LDS / row capacities sized for V rows of at most `mx`
             entries; `over` = the device words that report a longer row (None: mx is exact)"""
             if k2 != 1:
                 kk = min(k2, N, K)
+                if not qe_fits(mx):
+                    # (k2 lists of mx entries, ~10 bytes each, for one row: k2 = 64 holds rows of up to 255 entries, k2 = 32 of 511)
+                    raise ValueError("re_ranking on the GPU: k1=%d, k2=%d with a longest k-reciprocal row of %d entries does not fit the query "
+                                     "expansion's 160 KB of LDS (%d rows of that length are staged at once); use a smaller k2 or k1" % (k1, k2, mx, kk))
                 capQ = kk * mx
                 q_idx = torch.empty((nrows, capQ), dtype=torch.int32, device=dev)
                 q_val = torch.empty((nrows, capQ), dtype=torch.float16, device=dev)
@@ -505,6 +513,8 @@ def re_ranking_device(src, tgt, k1=20, k2=6, lambda_value=0.2, no_rerank=False, 
             # a miss are combined over the ranks -- maximum -- when they are read, `DistHandle.global_status`, so that all ranks redo
             # together; round 4 read the gathered v_nnz back here instead: one blocking read per split)
             guess = min(capV, _QE_GUESS.get(_qe_key(k1, group), 64))
+            if not qe_fits(guess):
+                guess = min(capV, 64)                    # (the + 25 % of a remembered guess passed the LDS: 64 entries fit at every k2; a miss is redone)
             tail(guess, status[2:4])
             # a miss redoes the tail sized by the longest row the kernel REPORTED (status[3]: exact over the rows it staged), not by the worst-case
             # capacity capV = (k1+1)(round(k1/2)+2) -- that one passes the 160 KB of LDS from k1 ~ 35 on; 0 (no report) falls back to a read of v_nnz

@@ -179,7 +179,7 @@ def test_comm_entry_points_world1_on_rccl():
 # mention.  The list may only SHRINK: an entry point leaves it when a test calls it by name, and a new export must arrive with such a test.
 _ONLY_THROUGH_WRAPPERS = """
 concat_segments_u64 dbscan_cc_dev dbscan_cc_workspace_bytes eps_compact eps_mean fill_u64 half_min invert_index jaccard_rows jaccard_segments
-jpeg_decode_batch jpeg_parse_close jpeg_parse_fill query_expand region_query_dev region_query_s_dev row_norms_f64
+jpeg_decode_batch jpeg_parse_close jpeg_parse_fill region_query_dev region_query_s_dev row_norms_f64
 source_rowmin_f16 topk_rank_introsort_arena_bytes topk_rank_introsort_flags_offset topk_rank_introsort_ws_bytes
 triplet_grad_combine triplet_grad_weights
 """.split()

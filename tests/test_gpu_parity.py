@@ -25,14 +25,7 @@ def L():
     return _lib.lib()
 
 
-def _sparse_to_dense(idx, val, nnz, N):
-    idx = idx.cpu().numpy(); val = val.cpu().numpy().view(np.uint16); nnz = nnz.cpu().numpy()
-    out = np.zeros((idx.shape[0], N), np.uint16)
-    for i in range(idx.shape[0]):
-        n = int(nnz[i])
-        assert np.all(np.diff(idx[i, :n]) > 0), "sparse row %d not sorted by column" % i
-        out[i, idx[i, :n]] = val[i, :n]
-    return out
+from rerank_grid_ref import sparse_to_dense as _sparse_to_dense  # noqa: E402  (sparse rows -> dense half bits; shared with tests/test_gpu_rerank_grid.py)
 
 
 # ------------------------------------------------------------------ exhaustive half functions

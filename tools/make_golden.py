@@ -116,6 +116,20 @@ def beq(a, b):
     return a.shape == b.shape and np.array_equal(a, b, equal_nan=(a.dtype.kind == "f"))
 
 
+def save_npz_stable(path, rec):
+    """np.savez_compressed with a fixed member time stamp: the same arrays give the same bytes on every run (numpy stamps each member
+    with the clock)"""
+    import io
+    import zipfile
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as zf:
+        for k, a in rec.items():
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asanyarray(a), allow_pickle=False)
+            info = zipfile.ZipInfo(k + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            zf.writestr(info, buf.getvalue())
+
+
 def exp_quirk_inputs():
     """Half inputs x where this host's numpy np.exp(half(-x)) is NOT the correctly rounded
     result (AVX512-FP16 SVML path).  Fixtures must not exercise them."""
@@ -552,6 +566,53 @@ def variant_fixtures(mod):
     return ok
 
 
+def kgrid_fixture(mod):
+    """The UNTOUCHED reference over the k1 / k2 / lambda / N range `re_ranking_device` accepts: the case table of
+    tests/rerank_grid_ref.py (k2 = 1, odd and tiny k1, k1 = 63, k2 up to 64, N <= k1, lambda in {0, 1, 1.5}) ->
+    tests/golden/rerank_kgrid.npz.  The oracle must equal the reference at every stage, in eps and in the labels at both rho; every
+    case must have the property it is there for.  Stored per case: sha256 of the inputs and of every stage, the first k1 + 1 rank
+    columns, eps / count / top_num and sklearn's labels at both rho (where top_num is 0 the reference's eps is the mean of an empty
+    slice -- NaN -- and sklearn refuses it: no labels), and final_dist itself up to N = 100."""
+    import warnings
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import rerank_grid_ref as grid
+    ok = True
+    rec = {"names": np.array([c.name for c in grid.CASES])}
+    for c in grid.CASES:
+        src, tgt = grid.inputs(c)
+        kw = dict(k1=c.k1, k2=c.k2, lambda_value=c.lam)
+        e, f, cap = run_ref(mod, src, tgt, False, **kw)
+        oe, of, st = ora.re_ranking(src, tgt, rank_mode="introsort", stages=True, **kw)
+        Kr = cap["rank"].shape[1]
+        chk = dict(euclid=beq(e, oe), rank=beq(cap["rank"], st["rank"][:, :Kr]), V=beq(cap["V"], st["V"]), V_qe=beq(cap["V_qe"], st["V_qe"]),
+                   jaccard=beq(cap["jaccard"], st["jaccard"]), final=beq(f, of))
+        vmax = grid.check_claims(c, cap, f)
+        p = c.name + "__"
+        rec.update({p + "sha_src": sha(src), p + "sha_tgt": sha(tgt), p + "rank": cap["rank"].astype(np.int32), p + "vmax": np.int32(vmax),
+                    p + "sha_euclid": sha(e), p + "sha_V": sha(cap["V"]), p + "sha_V_qe": sha(cap["V_qe"]), p + "sha_jaccard": sha(cap["jaccard"]),
+                    p + "sha_final": sha(f)})
+        if c.N <= grid.FULL_N:
+            rec[p + "final"] = f
+        for r, rho in enumerate(grid.RHOS):
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore")              # (mean of an empty slice when top_num is 0)
+                eps, cnt, top = eps_rule_ref(f, rho)
+            oeps, ocnt, otop = ora.eps_rule(f, rho)
+            good = (cnt, top) == (ocnt, otop) and (float(eps) == oeps or (top == 0 and np.isnan(eps) and np.isnan(oeps)))
+            rec.update({p + "eps%d" % r: np.float64(eps), p + "count%d" % r: np.int64(cnt), p + "top%d" % r: np.int64(top)})
+            if top > 0:
+                labels = DBSCAN(eps=eps, min_samples=4, metric="precomputed", n_jobs=8).fit_predict(f)
+                good = good and beq(labels.astype(np.int64), ora.dbscan(f, eps, 4))
+                rec[p + "labels%d" % r] = labels.astype(np.int64)
+            chk["eps+labels@%g" % rho] = bool(good)
+        print("kgrid %-24s oracle==reference: %s  longest V row %d" % (c.name, chk, vmax))
+        ok = ok and all(chk.values())
+    path = os.path.join(OUT, "rerank_kgrid.npz")
+    save_npz_stable(path, rec)
+    print("kgrid: %d cases, %d bytes" % (len(grid.CASES), os.path.getsize(path)))
+    return ok
+
+
 def wide_fixture(mod):
     """the UNTOUCHED reference at the bench's feature width -- N = 2000, Ns = 2000, d = 2048 on the hard set
     (tools/synth.hard_clustered, lambda = 0.3): the 2048-term float64 cdist sums (rerank.py:37,61), the introsort tie order at
@@ -748,6 +809,10 @@ def main():
         ok = wide_fixture(mod)
         print("ALL OK" if ok else "ORACLE MISMATCH")
         sys.exit(0 if ok else 1)
+    if "--only-kgrid" in sys.argv:        # regenerate just tests/golden/rerank_kgrid.npz
+        ok = kgrid_fixture(mod)
+        print("ALL OK" if ok else "ORACLE MISMATCH")
+        sys.exit(0 if ok else 1)
     if "--only-tiefree" in sys.argv:      # regenerate just tests/golden/rerank_tiefree_*.npz and rerank_var_*.npz
         ok = tiefree_fixture(mod)
         ok = variant_fixtures(mod) and ok
@@ -870,6 +935,7 @@ def main():
     ok = jpeg_fixture() and ok
     ok = plain_fixture() and ok
     ok = wide_fixture(mod) and ok
+    ok = kgrid_fixture(mod) and ok
     print("ALL OK" if ok else "ORACLE MISMATCH")
     sys.exit(0 if ok else 1)
 
