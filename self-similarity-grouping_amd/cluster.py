@@ -28,8 +28,20 @@ _MAX_COMPACT = 1 << 24
 from .dist import all_reduce_sum as _all_reduce, gather_rows, gather_varlen  # noqa: E402
 
 
+def _check_values(nan, inf, neg, dtype="float64"):
+    """sklearn's refusals of a precomputed distance matrix (check_array, then _check_precomputed), in its order"""
+    if nan:
+        raise ValueError("Input X contains NaN.")
+    if inf:
+        raise ValueError("Input X contains infinity or a value too large for dtype('%s')." % dtype)
+    if neg:
+        raise ValueError("Negative values in data passed to X.")
+
+
 def as_handle(X, device=None):
-    """numpy / torch matrix or handle -> DistHandle on the GPU."""
+    """numpy / torch matrix or handle -> DistHandle on the GPU.  A matrix (not a handle: those are built on the device and cost no host
+    read here) is refused with sklearn's ValueError when it holds NaN, infinity or a negative value.  A float32 matrix is held as
+    float64 and remembered as float32 (`eps_f32`): sklearn compares such a matrix with float32(eps), see `compare_eps`."""
     if isinstance(X, DistHandle):
         return X
     valid = getattr(X, "valid_handle", None)     # DeviceBackedArray: only the untouched, still read-only original carries one
@@ -40,16 +52,37 @@ def as_handle(X, device=None):
     if isinstance(X, np.ndarray):
         if X.ndim != 2 or X.shape[0] != X.shape[1]:
             raise ValueError("Precomputed distance matrix must be square, got shape %r" % (X.shape,))
+        if X.dtype.kind == "f":
+            _check_values(bool(np.isnan(X).any()), bool(np.isinf(X).any()), bool((X < 0).any()), X.dtype.name)
+        elif X.dtype.kind == "i":
+            _check_values(False, False, bool((X < 0).any()))
         if X.dtype == np.float16:
             return DistHandle(X.shape[0], 1, torch.from_numpy(np.ascontiguousarray(X)).to(device))
-        return DistHandle(X.shape[0], 2, torch.from_numpy(np.ascontiguousarray(X, dtype=np.float64)).to(device))
+        h = DistHandle(X.shape[0], 2, torch.from_numpy(np.ascontiguousarray(X, dtype=np.float64)).to(device))
+        h.eps_f32 = X.dtype == np.float32
+        return h
     if torch.is_tensor(X):
         if X.dim() != 2 or X.shape[0] != X.shape[1]:
             raise ValueError("Precomputed distance matrix must be square")
+        if X.is_floating_point():
+            _check_values(*torch.stack([torch.isnan(X).any(), torch.isinf(X).any(), (X < 0).any()]).tolist(), str(X.dtype)[6:])    # (one read)
         if X.dtype == torch.float16:
             return DistHandle(X.shape[0], 1, X.to(device).contiguous())
-        return DistHandle(X.shape[0], 2, X.to(device=device, dtype=torch.float64).contiguous())
+        h = DistHandle(X.shape[0], 2, X.to(device=device, dtype=torch.float64).contiguous())
+        h.eps_f32 = X.dtype == torch.float32
+        return h
     raise TypeError("unsupported distance matrix type %r" % type(X))
+
+
+def compare_eps(h, eps):
+    """The radius the region query (a float64 comparison) is given for the estimator's `eps`.  sklearn 1.7.2 keeps a float32 precomputed
+    matrix in float32 and evaluates `d <= eps` there, numpy casting the scalar to the array's dtype: float32(0.1) <= 0.1 holds on a float32
+    matrix and fails on its float64 copy.  d <= float32(eps) in float32 is d <= float64(float32(eps)) in float64.  Every other input --
+    float16 (which sklearn widens to float64), float64, re-rank handles -- compares with eps itself (tests/dbscan_grid_ref.py)."""
+    if getattr(h, "eps_f32", False):
+        with np.errstate(over="ignore"):
+            return float(np.float32(eps))
+    return float(eps)
 
 
 def _sampled_path():
@@ -446,6 +479,8 @@ def eps_rule_dbscan(X, rho, min_samples=4):
     if (not _sampled_path() or os.environ.get("SSG_EPS_FUSED", "1") == "0" or not rho > 0
             or N < 64 or top_guess <= 0):
         return two_calls()
+    if h.eps_f32:
+        return two_calls()                                    # a float32 matrix: DBSCAN.fit compares with float32(eps), which this chain never sees
     if h.group is not None:
         return _eps_rule_dbscan_sharded(L, h, rho, min_samples, two_calls)
     dev, st = h.device, stream()
@@ -526,7 +561,12 @@ def eps_rule_dbscan(X, rho, min_samples=4):
 
 
 class DBSCAN:
-    """sklearn.cluster.DBSCAN look-alike for metric='precomputed' running on the GPU."""
+    """sklearn.cluster.DBSCAN look-alike for metric='precomputed' running on the GPU.
+
+    The matrix must be SYMMETRIC (it is not checked).  Clusters are the connected components of the core points, numbered by their
+    smallest core index; on a symmetric matrix that is sklearn's visiting order, on an asymmetric one (a core k that holds i in no row
+    of its own) the two can differ.  NaN, infinity and negative values in a numpy / torch matrix raise ValueError as in sklearn; a
+    float32 matrix is compared with float32(eps) as sklearn does (`compare_eps`)."""
 
     def __init__(self, eps=0.5, *, min_samples=5, metric="euclidean", metric_params=None, algorithm="auto", leaf_size=30, p=None,
                  n_jobs=None):
@@ -550,7 +590,7 @@ class DBSCAN:
         L = _lib.lib()
         h = as_handle(X)
         dev, st, N = h.device, stream(), h.N
-        eps = float(self.eps)
+        eps = compare_eps(h, self.eps)
         cnt = torch.empty(h.nrows, dtype=torch.int32, device=dev)
         mx_rows = h.nrows
         if h.group is not None:

@@ -54,6 +54,7 @@ class DistHandle:
     _error = None
     _redo = None
     _k1 = None
+    eps_f32 = False        # a float32 matrix held as float64 (cluster.as_handle): DBSCAN compares it with float32(eps), as sklearn does
     sparse = None          # the sparse copy S of J' (re_ranking_device), or None; its consumers gate on the device-side overflow word
 
     def validate(self):

@@ -613,6 +613,46 @@ def kgrid_fixture(mod):
     return ok
 
 
+def dbscan_grid_fixture():
+    """sklearn's DBSCAN(metric='precomputed') over the min_samples / eps / dtype / N range `ssg_amd.cluster.DBSCAN` accepts: the case
+    table of tests/dbscan_grid_ref.py -> tests/golden/dbscan_grid.npz.  Per case: the sha256 of the regenerated matrix, and labels_ /
+    core_sample_indices_ (int32) of sklearn on the array exactly as the case passes it -- the same dtype, the same Python-float eps.
+    The cases of the one-read chain (`rho`) also store the reference's eps rule and sklearn's labels at its eps for each min_samples of
+    the chain tests.  The restatement, and on float64 input the C oracle, must equal sklearn; every case must have the property it is
+    in the table for."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import dbscan_grid_ref as grid
+    ok = True
+    rec = {"names": np.array([c.name for c in grid.CASES])}
+    for c in grid.CASES:
+        D = grid.matrix(c)
+        p = c.name + "__"
+        rec[p + "sha"] = sha(D)
+        m = grid.check_claims(c)
+        chk = {}
+        if c.eps > 0:
+            est = DBSCAN(eps=c.eps, min_samples=c.ms, metric="precomputed").fit(grid.as_numpy(grid.as_passed(c)) if c.container.startswith("numpy") else D)
+            rec[p + "labels"] = est.labels_.astype(np.int32)
+            rec[p + "core"] = est.core_sample_indices_.astype(np.int32)
+            chk["restatement"] = beq(est.labels_.astype(np.int64), m["labels"]) and beq(est.core_sample_indices_.astype(np.int64), m["core"].astype(np.int64))
+            if c.dtype == "float64":
+                chk["oracle"] = beq(ora.dbscan(D, c.eps, c.ms), m["labels"])
+        if c.rho is not None:
+            eps, cnt, top = grid.chain_reference(c)
+            rec.update({p + "chain_eps": np.float64(eps), p + "chain_count": np.int64(cnt), p + "chain_top": np.int64(top)})
+            for ms in grid.CHAIN_MS:
+                est = DBSCAN(eps=float(eps), min_samples=ms, metric="precomputed").fit(D)
+                rec[p + "chain_labels%d" % ms] = est.labels_.astype(np.int32)
+                lab, core = grid.dbscan_ref(D, float(eps), ms)
+                chk["chain ms=%d" % ms] = beq(est.labels_.astype(np.int64), lab) and beq(est.core_sample_indices_.astype(np.int64), core.astype(np.int64))
+        print("dbscan grid %-28s %s  hits %d clusters %d noise %d border %d" % (c.name, chk, m["nhits"], m["n_clusters"], m["n_noise"], m["border"]))
+        ok = ok and all(chk.values())
+    path = os.path.join(OUT, "dbscan_grid.npz")
+    save_npz_stable(path, rec)
+    print("dbscan grid: %d cases, %d bytes" % (len(grid.CASES), os.path.getsize(path)))
+    return ok
+
+
 def wide_fixture(mod):
     """the UNTOUCHED reference at the bench's feature width -- N = 2000, Ns = 2000, d = 2048 on the hard set
     (tools/synth.hard_clustered, lambda = 0.3): the 2048-term float64 cdist sums (rerank.py:37,61), the introsort tie order at
@@ -801,6 +841,11 @@ def main():
         sys.exit(0 if ok else 1)
     if "--only-eval" in sys.argv:         # regenerate just tests/golden/eval_cases.npz
         ok = eval_fixture()
+        print("ALL OK" if ok else "ORACLE MISMATCH")
+        sys.exit(0 if ok else 1)
+    if "--only-dbscan-grid" in sys.argv:  # regenerate just tests/golden/dbscan_grid.npz
+        ora.build(force=False)
+        ok = dbscan_grid_fixture()
         print("ALL OK" if ok else "ORACLE MISMATCH")
         sys.exit(0 if ok else 1)
     ora.build(force=True)
