@@ -443,6 +443,25 @@ int ssg_rank_metrics(const float* dist, int m, int n, int64_t ld, const int32_t*
 int ssg_rank_metrics_all(const float* dist, int m, int n, int64_t ld, const int32_t* qid, const int32_t* qcam, const int32_t* gid,
                          const int32_t* gcam, int separate_cams, int32_t* first_rank, double* ap, int32_t* overflow, int32_t* nm_before,
                          int32_t* nmatch, int nm_cap, ssg_stream_t stream);
+/* the single-gallery-shot protocol ('cuhk03': ranking.py:10-16,53-66, ten random one-entry-per-identity gallery subsets per query) for a
+ * chunk of mq queries, in three stages over one workspace of ssg_cmc_sgs_workspace_bytes(mq, n, G) bytes (0: shape outside the limits
+ * n <= 131072, G <= 16384).  gden [n] = dense gallery identity 0..G-1, qden [mq] = the dense identity of the query's id or -1; no
+ * identity may have more than ssg_cmc_sgs_max_group() = 16384 gallery entries (the caller checks).
+ * groups: per query the valid entries grouped by identity, each group ascending in (distance, gallery index), the groups in order of
+ *         first appearance.
+ * draws:  numpy's legacy randint on the supplied 32-bit MT19937 words [word_base, word_base + nwords) of the stream (a group of s > 1
+ *         entries takes the first word w with w & (2^bit_length(s-1) - 1) <= s - 1), queries -> 10 repeats -> groups.  state [4]:
+ *         [0] words consumed so far (carried from chunk to chunk), [1] / [2] query and draw to resume at, [3] set when the words ran
+ *         out: launch again with words from state[0] on.  The caller zeroes state[1..3] before a chunk's first launch.
+ * counts: k [mq, 10] = other identities whose drawn entry is ordered before the drawn true match; -1: no valid true match. */
+size_t ssg_cmc_sgs_workspace_bytes(int mq, int n, int G);
+int ssg_cmc_sgs_max_group(void);
+int ssg_cmc_sgs_groups(const float* dist, int mq, int n, int64_t ld, const int32_t* qid, const int32_t* qcam, const int32_t* qden,
+                       const int32_t* gid, const int32_t* gcam, const int32_t* gden, int G, int separate_cams, void* ws, size_t ws_bytes,
+                       ssg_stream_t stream);
+int ssg_cmc_sgs_draws(void* ws, size_t ws_bytes, int mq, int n, int G, const uint32_t* words, uint64_t word_base, uint64_t nwords,
+                      uint64_t* state, ssg_stream_t stream);
+int ssg_cmc_sgs_counts(const void* ws, size_t ws_bytes, int mq, int n, int G, int32_t* k, ssg_stream_t stream);
 
 /* ---- float32 re-ranking variant "re_ranking_init" (reid/rerank.py:171-234 == reid/rerank_initial.py:40-99) */
 /* out[i,j] = 2 - 2<x_i,y_j> (rerank.py:174-182); d % 32 == 0, n % 64 == 0; zeros = n floats of 0 */
