@@ -463,6 +463,32 @@ int ssg_cmc_sgs_draws(void* ws, size_t ws_bytes, int mq, int n, int G, const uin
                       uint64_t* state, ssg_stream_t stream);
 int ssg_cmc_sgs_counts(const void* ws, size_t ws_bytes, int mq, int n, int G, int32_t* k, ssg_stream_t stream);
 
+/* ---- KISSME metric learning (reid/metric_learning/kissme.py:33-55; csrc/kissme.hip).  The reference visits the pairs (a, b), a < b,
+ * in the order of its masked meshgrid: b ascending, a ascending inside b.  den [n] = dense class id of every row, 0 .. G-1
+ * (1 <= G <= n <= 2^24); ids outside that range are never dereferenced, the outputs are then unspecified.
+ * index:       a stable counting sort -- cls_ptr [G+1], members [n] (each class's rows ascending), rank [n] (position of a row inside
+ *              its class) -- and two int64 exclusive scans over b: m_scan [n+1] counts the matching pairs (a < b) of the rows below b,
+ *              nm_scan [n+1] the non-matching ones (b - rank[b] per row); m_scan[n] and nm_scan[n] are the two totals.
+ * match_pairs: ia, ib [P1], P1 = m_scan[n]: every matching pair in the reference's order; slot m_scan[b] + j holds
+ *              (members[cls_ptr[den[b]] + j], b).
+ * unrank:      ia[t], ib[t] = the non-matching pair at position pos[t] of that order (T positions, int64).  b by bisection of nm_scan,
+ *              q = pos[t] - nm_scan[b], then with L the member list of b's class and j the smallest index with L[j] - j > q: a = q + j.
+ *              A position outside [0, nm_scan[n]) gives (-1, -1).
+ * All outputs are functions of the inputs alone (the one atomic counts class sizes). */
+int ssg_kissme_index(const int32_t* den, int n, int G, int32_t* cls_ptr, int32_t* members, int32_t* rank, int64_t* m_scan,
+                     int64_t* nm_scan, ssg_stream_t stream);
+int ssg_kissme_match_pairs(const int32_t* den, const int32_t* rank, const int32_t* cls_ptr, const int32_t* members,
+                           const int64_t* m_scan, int n, int G, int64_t P1, int32_t* ia, int32_t* ib, ssg_stream_t stream);
+int ssg_kissme_unrank(const int64_t* pos, int64_t T, const int32_t* den, const int32_t* rank, const int32_t* cls_ptr,
+                      const int32_t* members, const int64_t* nm_scan, int n, int G, int32_t* ia, int32_t* ib, ssg_stream_t stream);
+/* C [d, d] float64 = (sum over the P pairs of s s^T) / divisor, s = (double) X[ia[p]] - (double) X[ib[p]]; X [n, ldx] float32,
+ * 16-byte aligned, ldx >= d, ldx % 4 == 0; 16 <= d <= 16384, d % 16 == 0 (the caller zero-pads the columns); any P >= 1 (the last slice
+ * of 16 pairs is masked); a pair with an index outside [0, n) contributes nothing.  v_mfma_f64_16x16x4_f64, one workgroup per
+ * 128 x 128 tile on or above the diagonal walking all P pairs: no split of the pair axis, no workspace, no float atomics -- the same
+ * call gives the same bits, and C[i][j] and C[j][i] are the same bits (one is a copy of the other). */
+int ssg_pairdiff_cov_f64(const float* X, int n, int64_t ldx, const int32_t* ia, const int32_t* ib, int64_t P, int d, double divisor,
+                         double* C, ssg_stream_t stream);
+
 /* ---- float32 re-ranking variant "re_ranking_init" (reid/rerank.py:171-234 == reid/rerank_initial.py:40-99) */
 /* out[i,j] = 2 - 2<x_i,y_j> (rerank.py:174-182); d % 32 == 0, n % 64 == 0; zeros = n floats of 0 */
 int ssg_cosine_dist_f32(const float* x, const float* y, int m, int n, int d, const float* zeros, float* out, ssg_stream_t stream);

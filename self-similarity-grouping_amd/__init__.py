@@ -40,6 +40,12 @@ def __getattr__(name):   # lazy: torch import only when the compute surface is t
     if name in ("cmc", "mean_ap", "evaluate_all", "evaluate_same_cams_all", "Evaluator", "single_shot_ranks"):
         from . import ranking
         return getattr(ranking, name)
+    if name in ("get_metric", "KISSME", "Euclidean", "validate_cov_matrix"):       # reid/metric_learning/ (the two in-tree learners)
+        from . import metric_learning
+        return getattr(metric_learning, name)
+    if name == "DistanceMetric":
+        from . import dist_metric
+        return dist_metric.DistanceMetric
     if name in ("find_metric_threshold", "cal_classification_error", "findMetricThreshold_MPI", "CalClassificationError_MPI", "VerificationResult"):
         from . import verification
         return getattr(verification, name)
