@@ -527,8 +527,12 @@ int ssg_preprocess_u8(const uint8_t* src, int B, int h, int w, int H, int W, con
  *   coef  workspace int16 [total_blocks][64] (zeroed by the call), planes workspace uint8 (sum of 64 * blocks), max_blocks / max_pixels =
  *         largest component (in blocks) / image (in pixels) of the batch; out: RGB bytes, H * W * 3 per image at its offset.
  *   status int32 [nimg] (zeroed by the call; round 4): non-zero = damaged entropy-coded data (bit 0: a zero run past coefficient 63,
- *         bit 1: a segment ran out of data before its MCUs were decoded) -- the pixels of such a file are not libjpeg's; the caller
- *         hands it to the reference's decoder (Pillow), which warns / raises like the reference. */
+ *         bit 1: a segment ran out of data before its MCUs were decoded), or data on which builds of libjpeg differ (bit 2: a
+ *         dequantised coefficient or a pass-1 IDCT output outside int16, or a pass-2 IDCT output outside [-512, 511] -- jidctint.c
+ *         wraps there, libjpeg-turbo's SIMD IDCT works in 16 bits and saturates; no 8-bit encoder emits such values) -- the pixels of
+ *         such a file are not libjpeg's, or not every libjpeg's; the caller hands it to the reference's decoder (Pillow), which
+ *         warns / raises like the reference.  An unknown Huffman code is no flag by itself: it decodes to 0 after 17 bits like in
+ *         jdhuff.c, and what follows decides. */
 int ssg_jpeg_decode_batch(const uint8_t* ecs, const int64_t* segs, int nseg, const int64_t* imgs, int nimg, const uint16_t* look,
                           const int32_t* maxcode, const int32_t* valoff, const uint8_t* vals, const uint16_t* qts, int16_t* coef,
                           int64_t total_blocks, int max_blocks, uint8_t* planes, int max_pixels, uint8_t* out, int32_t* status,

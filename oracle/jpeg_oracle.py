@@ -12,6 +12,10 @@ __graft_entry__.smoke() use it as the checker.
 Supported (what the GPU decoder takes; anything else is left to Pillow by the product as well): baseline / extended
 sequential Huffman JPEG (SOF0 / SOF1), 8 bit, 1 component or 3 components (YCbCr) with luma sampling 1x1, 2x1 or 2x2 and
 1x1 chroma, optional restart intervals.
+
+Damaged entropy-coded data: `decode` raises `Damaged` by the rule of the kernels' per-image status word (include/ssg_hip.h) -- a zero
+run past coefficient 63, a segment that ends before its MCUs are decoded, or values on which builds of libjpeg differ (a dequantised
+coefficient or a pass-1 IDCT output outside int16, a pass-2 output outside [-512, 511]).  Whatever it returns equals Pillow.
 """
 import numpy as np
 
@@ -21,6 +25,10 @@ ZIGZAG = np.array([0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 1
 
 class Unsupported(ValueError):
     """not a file of the supported class (progressive, arithmetic, 12 bit, CMYK, unusual sampling ...)"""
+
+
+class Damaged(ValueError):
+    """the entropy-coded data cannot be decoded to what every libjpeg build produces (the product hands such a file to Pillow)"""
 
 
 def parse(data):
@@ -129,6 +137,7 @@ def huff_tables(bits, vals):
 class _Bits:
     def __init__(self, data):
         self.d, self.pos, self.acc, self.n = data, 0, 0, 0
+        self.pad = 0                    # zero bits fed since the data ran out; they sit at the end of acc, so n < pad = some were consumed
 
     def _fill(self):
         while self.n <= 24:
@@ -139,10 +148,10 @@ class _Bits:
                     if nx == 0:
                         self.pos += 1
                     else:               # a marker: feed zeros (libjpeg "insufficient data" behaviour)
-                        self.pos -= 1; b = 0
+                        self.pos -= 1; b = 0; self.pad += 8
                         self.d = self.d[:self.pos]
             else:
-                b = 0
+                b = 0; self.pad += 8
             self.acc = (self.acc << 8) | b; self.n += 8
 
     def get(self, k):
@@ -158,7 +167,7 @@ class _Bits:
         code, l = self.get(1), 1
         while code > maxcode[l]:
             code = (code << 1) | self.get(1); l += 1
-            if l > 16:
+            if l > 16:                  # 17 bits consumed: jdhuff.c's walk stops on the maxcode[17] sentinel
                 return 0
         return vals[code + valoff[l]]
 
@@ -168,7 +177,8 @@ def _extend(r, s):
 
 
 def decode_coefficients(hdr):
-    """-> per component int16 [blocks_h, blocks_w, 64] (natural order, quantised), MCU-padded"""
+    """-> per component int16 [blocks_h, blocks_w, 64] (natural order, quantised), MCU-padded; raises Damaged after the last segment
+    when a zero run passed coefficient 63 or a segment consumed bits behind its end"""
     comps, W, H = hdr["comps"], hdr["width"], hdr["height"]
     hmax = max(c[1] for c in comps); vmax = max(c[2] for c in comps)
     mcux = (W + 8 * hmax - 1) // (8 * hmax); mcuy = (H + 8 * vmax - 1) // (8 * vmax)
@@ -187,6 +197,7 @@ def decode_coefficients(hdr):
     segs.append(ecs[start:])
     ri = hdr["restart_interval"] or mcux * mcuy
     mcu = 0
+    bad = []
     for seg in segs:
         br = _Bits(seg)
         pred = [0] * len(comps)
@@ -202,18 +213,24 @@ def decode_coefficients(hdr):
                         s = br.decode(dct[td])
                         if s:
                             pred[ci] += _extend(br.get(s), s)
-                        blk[0] = np.int16(pred[ci])
+                        blk[0] = np.int16(((pred[ci] + 32768) & 0xFFFF) - 32768)      # (JCOEF is a short: damaged data can wrap it)
                         k = 1
                         while k < 64:
                             rs = br.decode(act[ta]); r, s = rs >> 4, rs & 15
                             if s:
                                 k += r
+                                if k > 63:
+                                    bad.append("zero run past coefficient 63")
                                 blk[ZIGZAG[k & 63]] = np.int16(_extend(br.get(s), s)); k += 1
                             elif r == 15:
                                 k += 16
                             else:
                                 break
             mcu += 1
+        if br.n < br.pad:
+            bad.append("segment ended before its MCUs were decoded")
+    if bad:
+        raise Damaged(bad[0])
     return coef
 
 
@@ -227,8 +244,10 @@ def _range_limit_idct(x):
     return np.where(i < 128, i + 128, np.where(i < 512, 255, np.where(i < 896, 0, i - 896))).astype(np.uint8)
 
 
-def idct_islow(coef, qt):
-    """jidctint.c jpeg_idct_islow on [..., 64] quantised coefficients -> uint8 [..., 8, 8]"""
+def idct_islow(coef, qt, margins=None):
+    """jidctint.c jpeg_idct_islow on [..., 64] quantised coefficients -> uint8 [..., 8, 8].  Raises Damaged outside the ranges on which
+    the C code and libjpeg-turbo's SIMD code agree; `margins` (a dict) collects the largest magnitudes seen: dequantised coefficient,
+    pass-1 output, and the smallest / largest pass-2 output before the +128 shift."""
     F = dict(a=2446, b=3196, c=4433, d=6270, e=7373, f=9633, g=12299, h=15137, i=16069, j=16819, k=20995, l=25172)
 
     def one_d(v0, v1, v2, v3, v4, v5, v6, v7, sh0):
@@ -249,14 +268,20 @@ def idct_islow(coef, qt):
     x = x.reshape(x.shape[:-1] + (8, 8))                     # [row, col]
     ws = np.stack(one_d(*[x[..., r, :] for r in range(8)], 13 - 2), axis=-2)     # pass 1: columns (over the row index)
     out = np.stack(one_d(*[ws[..., :, c] for c in range(8)], 13 + 2 + 3), axis=-1)   # pass 2: rows
+    if margins is not None and x.size:
+        margins["dequantised"] = max(margins.get("dequantised", 0), int(np.abs(x).max()))
+        margins["pass1"] = max(margins.get("pass1", 0), int(np.abs(ws).max()))
+        margins["pass2_min"] = min(margins.get("pass2_min", 0), int(out.min())); margins["pass2_max"] = max(margins.get("pass2_max", 0), int(out.max()))
+    if x.size and (x.min() < -32768 or x.max() > 32767 or ws.min() < -32768 or ws.max() > 32767 or out.min() < -512 or out.max() > 511):
+        raise Damaged("IDCT values outside the range on which libjpeg builds agree")
     return _range_limit_idct(out)
 
 
-def _planes(hdr):
+def _planes(hdr, margins=None):
     coef = decode_coefficients(hdr)
     planes = []
     for (cid, h, v, tq), cf in zip(hdr["comps"], coef):
-        px = idct_islow(cf, hdr["qt"][tq])                   # [by, bx, 8, 8]
+        px = idct_islow(cf, hdr["qt"][tq], margins)                   # [by, bx, 8, 8]
         planes.append(px.transpose(0, 2, 1, 3).reshape(cf.shape[0] * 8, cf.shape[1] * 8))
     return planes
 
@@ -292,11 +317,11 @@ def _upsample_h2v2(p, dw, dh):
     return out.astype(np.uint8)
 
 
-def decode(data):
-    """JPEG file bytes -> uint8 [H, W, 3] == np.asarray(Image.open(...).convert('RGB'))"""
+def decode(data, margins=None):
+    """JPEG file bytes -> uint8 [H, W, 3] == np.asarray(Image.open(...).convert('RGB')); raises Damaged (module docstring)"""
     hdr = parse(data)
     W, H, comps = hdr["width"], hdr["height"], hdr["comps"]
-    planes = _planes(hdr)
+    planes = _planes(hdr, margins)
     if len(comps) == 1:
         y = planes[0][:H, :W]
         return np.stack([y, y, y], axis=-1)

@@ -8,7 +8,8 @@
 //                    maxcode walk behind it, byte-stuffing removed on the fly -- writing the non-zero quantised coefficients
 //                    in natural order.  Sequential per segment by nature; the parallelism is across the images of a batch;
 //   idct_kernel      one thread per 8x8 block: dequantisation + the "islow" integer inverse DCT of jidctint.c
-//                    (CONST_BITS = 13, PASS1_BITS = 2, the library's default) + its range-limit table;
+//                    (CONST_BITS = 13, PASS1_BITS = 2, the library's default) + its range-limit table; values outside the range on
+//                    which the C code and libjpeg-turbo's SIMD code agree (damaged data only) are flagged per image;
 //   colour_kernel    one thread per pixel: "fancy" (triangle filter) chroma upsampling of jdsample.c with the context rows of
 //                    jdmainct.c (h2v1 / h2v2; plain replication for components at most 2 samples wide) and the 16-bit
 //                    fixed-point YCbCr -> RGB conversion of jdcolor.c; grayscale is replicated like convert('RGB') does.
@@ -78,7 +79,9 @@ __device__ __forceinline__ int decode_symbol(BitReader& br, const Tables& t, int
   int l = 9;
   int code = (int)br.peek(9);
   while (l <= 16 && code > mc[l]) { l++; code = (int)br.peek(l); }
-  if (l > 16) { br.n -= 16; return 0; }                      // a code no table holds (corrupt data): libjpeg returns 0 as well
+  // a code no table holds (corrupt data): libjpeg returns 0 as well -- after 17 bits: jpeg_huff_decode's walk only stops on the
+  // maxcode[17] sentinel (HUFF_DECODE_FAST of libjpeg-turbo alike), so the next symbol starts one bit behind the 16 compared here
+  if (l > 16) { br.n -= 17; return 0; }
   br.n -= l;
   return (int)t.vals[tab * 256 + ((code + t.valoff[tab * 17 + l]) & 0xff)];
 }
@@ -158,7 +161,7 @@ __device__ __forceinline__ void idct8(const int v0, const int v1, const int v2, 
 
 // grid.y = image * 3 + component, grid.x * 64 threads over the component's blocks
 __global__ __launch_bounds__(64) void idct_kernel(const int64_t* __restrict__ imgs, const int16_t* __restrict__ coef, const uint16_t* __restrict__ qts,
-                                                  uint8_t* __restrict__ planes) {
+                                                  uint8_t* __restrict__ planes, int32_t* __restrict__ status) {
   const int img = (int)blockIdx.y / 3, ci = (int)blockIdx.y % 3;
   const int64_t* im = imgs + (int64_t)img * IMG_WORDS;
   if (ci >= (int)im[I_NCOMP]) return;
@@ -169,15 +172,21 @@ __global__ __launch_bounds__(64) void idct_kernel(const int64_t* __restrict__ im
   const int16_t* blk = coef + (cd[C_COEF] + b) * 64;
   const uint16_t* qt = qts + cd[C_QT] * 64;
   int ws[8][8];
+  // Values no 8-bit encoder emits, on which builds of libjpeg differ (jidctint.c keeps 32+ bits and wraps in its range-limit table;
+  // the SIMD islow IDCT of libjpeg-turbo multiplies coefficient x quantiser in 16 bits, packs the pass-1 workspace to 16 bits and
+  // saturates its output): a dequantised coefficient or a pass-1 output outside int16, or a pass-2 output outside [-512, 511] (where
+  // `x & 1023` into the table and saturation part ways).  Such a block is flagged (status bit 2) and the file goes to the reference's
+  // decoder; inside these ranges every build computes the same bytes.
+  unsigned oob = 0;
   // pass 1: columns (index = row), dequantised input
 #pragma unroll
   for (int c = 0; c < 8; c++) {
     int v[8], o[8];
 #pragma unroll
-    for (int r = 0; r < 8; r++) v[r] = (int)blk[r * 8 + c] * (int)qt[r * 8 + c];
+    for (int r = 0; r < 8; r++) { v[r] = (int)blk[r * 8 + c] * (int)qt[r * 8 + c]; oob |= ((unsigned)v[r] + 32768u) >> 16; }
     idct8(v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], 13 - 2, o);
 #pragma unroll
-    for (int r = 0; r < 8; r++) ws[r][c] = o[r];
+    for (int r = 0; r < 8; r++) { ws[r][c] = o[r]; oob |= ((unsigned)o[r] + 32768u) >> 16; }
   }
   const int by = b / bw, bx = b - by * bw;
   uint8_t* dst = planes + cd[C_PLANE] + (int64_t)(by * 8) * cd[C_PITCH] + bx * 8;
@@ -186,10 +195,13 @@ __global__ __launch_bounds__(64) void idct_kernel(const int64_t* __restrict__ im
   for (int r = 0; r < 8; r++) {
     int o[8];
     idct8(ws[r][0], ws[r][1], ws[r][2], ws[r][3], ws[r][4], ws[r][5], ws[r][6], ws[r][7], 13 + 2 + 3, o);
+#pragma unroll
+    for (int c = 0; c < 8; c++) oob |= ((unsigned)o[c] + 512u) >> 10;
     const unsigned lo = range_limit_idct(o[0]) | (range_limit_idct(o[1]) << 8) | (range_limit_idct(o[2]) << 16) | (range_limit_idct(o[3]) << 24);
     const unsigned hi = range_limit_idct(o[4]) | (range_limit_idct(o[5]) << 8) | (range_limit_idct(o[6]) << 16) | (range_limit_idct(o[7]) << 24);
     *reinterpret_cast<uint2*>(dst + (int64_t)r * cd[C_PITCH]) = make_uint2(lo, hi);
   }
+  if (oob) atomicOr(status + img, 4);
 }
 
 // chroma sample of output pixel (x, y): jdsample.c fancy upsampling (dw x dh real samples in a plane of pitch `pitch`)
@@ -255,8 +267,10 @@ using namespace ssg;
 //   look / maxcode / valoff / vals    derived Huffman tables (jdhuff.c jpeg_make_d_derived_tbl), qts uint16 [nqt][64] natural order
 //   coef         workspace int16 [total blocks][64] (zeroed here), planes workspace uint8, out uint8 RGB pixels (H x W x 3 per image)
 //   status       int32 [nimg] (zeroed here): non-zero = the file's entropy-coded data is damaged (bit 0: a zero run past coefficient 63,
-//                bit 1: a segment ended before its MCUs were decoded); its pixels are then NOT what libjpeg produces -- the caller re-decodes
-//                such files with the reference's decoder, which warns / raises as the reference does
+//                bit 1: a segment ended before its MCUs were decoded) or holds values on which builds of libjpeg differ (bit 2: a dequantised
+//                coefficient or a pass-1 IDCT output outside int16, a pass-2 IDCT output outside [-512, 511]); its pixels are then NOT
+//                what libjpeg produces -- the caller re-decodes such files with the reference's decoder, which warns / raises as the
+//                reference does
 extern "C" int ssg_jpeg_decode_batch(const uint8_t* ecs, const int64_t* segs, int nseg, const int64_t* imgs, int nimg, const uint16_t* look,
                                      const int32_t* maxcode, const int32_t* valoff, const uint8_t* vals, const uint16_t* qts, int16_t* coef,
                                      int64_t total_blocks, int max_blocks, uint8_t* planes, int max_pixels, uint8_t* out, int32_t* status, hipStream_t stream) {
@@ -268,7 +282,7 @@ extern "C" int ssg_jpeg_decode_batch(const uint8_t* ecs, const int64_t* segs, in
   SSG_HIP(hipMemsetAsync(status, 0, (size_t)nimg * sizeof(int32_t), stream));
   jpeg::Tables t{look, maxcode, valoff, vals};
   hipLaunchKernelGGL(jpeg::huffman_kernel, dim3((nseg + 63) / 64), dim3(64), 0, stream, ecs, segs, nseg, imgs, t, coef, status);
-  hipLaunchKernelGGL(jpeg::idct_kernel, dim3((max_blocks + 63) / 64, nimg * 3), dim3(64), 0, stream, imgs, coef, qts, planes);
+  hipLaunchKernelGGL(jpeg::idct_kernel, dim3((max_blocks + 63) / 64, nimg * 3), dim3(64), 0, stream, imgs, coef, qts, planes, status);
   hipLaunchKernelGGL(jpeg::colour_kernel, dim3((max_pixels + 255) / 256, nimg), dim3(256), 0, stream, imgs, planes, out);
   SSG_LAUNCH_CHECK("jpeg kernels");
   return SSG_OK;

@@ -6,6 +6,8 @@
 // incl. its padding, coefficients, planes, tables, pixels), undefined arithmetic, or a segment that does not terminate.
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
+#include <string>
 #include <vector>
 #include "../../self-similarity-grouping_amd/csrc/jpeg_host.hip"     // (brings hip_runtime.h for the host)
 void ssg_set_error(const char*, ...) {}
@@ -57,7 +59,7 @@ extern "C" int LLVMFuzzerTestOneInput(const uint8_t* data, size_t size) {
     for (unsigned y = 0; y < 3; y++)                      // grid (ceil(max_blocks / 64), nimg * 3) x 64 threads
       for (int64_t b = 0; b < (c[6] + 63) / 64 * 64; b++) {
         fz_blockIdx.x = (unsigned)b; fz_blockIdx.y = y;
-        ssg::jpeg::idct_kernel(imgs.data(), coef.data(), qts.data(), planes.data());
+        ssg::jpeg::idct_kernel(imgs.data(), coef.data(), qts.data(), planes.data(), status.data());
       }
     fz_blockIdx.y = 0;
     for (int64_t px = 0; px < (c[9] + 255) / 256 * 256; px++) {   // grid (ceil(max_pixels / 256), nimg) x 256 threads
@@ -71,11 +73,12 @@ extern "C" int LLVMFuzzerTestOneInput(const uint8_t* data, size_t size) {
 }
 
 #ifdef FZ_MAIN
-// jpeg_device_host <in.jpg> <out.rgb>: the kernels' source text as a host decoder (tests/test_oracle_golden.py compares it with Pillow).
-// exit 0 = decoded, 3 = the parser hands the file to Pillow, 4 = the Huffman kernel flagged damaged data
-int main(int argc, char** argv) {
-  if (argc != 3) return 2;
-  FILE* f = fopen(argv[1], "rb");
+// jpeg_device_host <in.jpg> <out.rgb>: the kernels' source text as a host decoder (tests/jpeg_cases_ref.py builds it; the JPEG host tests
+// compare it with Pillow).  exit 0 = decoded, 3 = the parser hands the file to Pillow, 4 = a kernel flagged the file (any bit of its status
+// word: damaged entropy-coded data, or data on which libjpeg builds differ -- include/ssg_hip.h)
+// jpeg_device_host --dir <dir> <n>: the same for <dir>/0.jpg .. <dir>/<n-1>.jpg in one process -> <dir>/<i>.rgb, one code per line on stdout
+static int decode_file(const char* in, const char* outp) {
+  FILE* f = fopen(in, "rb");
   if (!f) return 2;
   std::vector<uint8_t> buf;
   uint8_t tmp[65536];
@@ -84,12 +87,26 @@ int main(int argc, char** argv) {
   fclose(f);
   std::vector<uint8_t> px;
   g_pixels = &px;
+  g_status = -1;
   LLVMFuzzerTestOneInput(buf.data(), buf.size());
+  g_pixels = nullptr;
   if (g_status < 0) return 3;
   if (g_status) return 4;
-  f = fopen(argv[2], "wb");
+  f = fopen(outp, "wb");
+  if (!f) return 2;
   fwrite(px.data(), 1, px.size(), f);
   fclose(f);
   return 0;
+}
+int main(int argc, char** argv) {
+  if (argc == 4 && std::string(argv[1]) == "--dir") {
+    for (int i = 0; i < atoi(argv[3]); i++) {
+      const std::string b = std::string(argv[2]) + "/" + std::to_string(i);
+      printf("%d\n", decode_file((b + ".jpg").c_str(), (b + ".rgb").c_str()));
+    }
+    return 0;
+  }
+  if (argc != 3) return 2;
+  return decode_file(argv[1], argv[2]);
 }
 #endif
