@@ -23,8 +23,9 @@
 // and replaces the residual; its pixel operand (this wave's 32 pixels x CIN channels) is loaded straight into MFMA fragments.
 //
 // Layer1 (C = 256, MID = 64, 32-pixel rows, TH = 4): 4 waves, 2 workgroups per CU (<= 80 KB of LDS each) -- one's loads run under
-// the other's multiplies.  Layer2 (C = 512, MID = 128, 16-pixel rows, TH = 8): the 128-channel halo intermediate alone is 85 KB,
-// so ONE 8-wave workgroup per CU (150 KB): phase 2 = 4 pixel tiles x 2 channel groups, phase 3 = a wave pair per pixel tile, the
+// the other's multiplies.  Layer2 (C = 512, MID = 128, 16-pixel rows, TH = 8) has two instances: bottleneck_halves_kernel below (4 waves,
+// y1 in channel halves, 2 workgroups per CU: the default) and the 8-wave one of this kernel (SSG_BN_L2_WAVES=8): the 128-channel halo
+// intermediate alone is 85 KB, so ONE 8-wave workgroup per CU (150 KB): phase 2 = 4 pixel tiles x 2 channel groups, phase 3 = a wave pair per pixel tile, the
 // epilogue patches take over the dead W3 stages; its phases are serial on a CU (measured 0.75 -> 0.62 ms per block).
 // All operand tiles are staged global -> registers -> LDS with the loads several k-tiles ahead (register rings), one barrier per
 // stage:
@@ -602,12 +603,370 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void bottleneck_kernel(Pa
   SSG_BN_STAMP(5)
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Layer2 in channel halves: the same block, the same 128-pixel tile, as a 4-wave workgroup in <= 80 KB of LDS, so that
+// two workgroups share a CU and one's loads, stores and epilogue arithmetic run under the other's multiplies (what the layer1 instance
+// lives on).  Measured at B = 1000, interleaved with the 8-wave instance: 1.13 -> 1.01 ms per block.
+//   * y1 in two channel halves: conv2 reduces chunk -> tap -> channel, chunks 0-1 read only y1 channels 0-63, chunks 2-3 only 64-127.
+//     Phase 1 computes all 128 channels in ONE pass over x (every wave owns a channel tile of each half); half 0 goes to LDS (272-byte
+//     pixel rows, 160 halo pixels = 43.5 KB) and feeds 18 (chunk, tap) k-tiles of conv2 while the accumulators of half 1 stay parked in
+//     registers (48 per lane); then half 1 takes over the same LDS rows for the other 18 k-tiles, into the same conv2 accumulators.
+//     (A second phase-1 pass for half 1 instead of the parked registers reads x twice: HBM-bound at 0.98 ms, no faster than 8 waves.)
+//   * phase-1 stages: whole 128-byte lines, rows unpadded and XOR-swizzled (two padded stages of 288 rows are 1 KB too large).
+//   * y2 never lives in LDS as rows: each 32 x 32 accumulator tile turns through a wave-private patch (scale, bias, ReLU, encode as
+//     before) and comes back as the MFMA fragments of conv3's pixel operand: 8 k-steps x (hi + lo) = 64 registers.
+//   * conv3 + epilogue in four passes of 128 output channels, each over the whole K = 128 in four 32-channel stages (the W2 stage
+//     shape and buffers); the epilogue is the code path of the kernel above.
+// Every accumulator sees the same products in the same order as in the 8-wave instance: bit-identical.
+template <int C, int MID, int IW, int TH>
+struct CfgH {
+  static constexpr int NW = 4, NTHR = NW * 64, HROWS = TH + 2, NPIX1 = HROWS * IW, NPIX = TH * IW;
+  static constexpr int MH = MID / 2;                                    // y1 channels per half
+  // phase-1 k-tiles: whole 128-byte lines, rows unpadded (two padded stages do not fit), 16-byte chunks XOR-swizzled with (row >> 1) & 7
+  static constexpr int K1T = 32, P1T = K1T * 4, CPR1 = 8, RPP1 = NTHR / CPR1;
+  static constexpr int XROWS = NPIX1, BUF1 = (XROWS + MID) * P1T;       // phase-1 stage: x rows, then W1 rows
+  static constexpr int NK1 = C / K1T, PD1 = 2;
+  static constexpr int PYH = MH * 4 + 16;                               // LDS pitch of a y1 pixel row of one half
+  static constexpr int ZERO_OFF = NPIX1 * PYH;                          // conv2's left / right padding
+  static constexpr int P2 = 144, W2_OFF = (ZERO_OFF + PYH + 255) / 256 * 256, BUF2 = MID * P2;   // W2 stages, later the W3 stages
+  static constexpr int NK2H = (MH / 32) * 9, PD2 = 3;                   // (chunk, tap) k-tiles of conv2 per half
+  static constexpr int NCP = 128, NPASS = C / NCP, KT3 = MID / 32;      // conv3: output channels per pass, passes, 32-channel stages per pass
+  static constexpr int EP = 36, PATCH = 32 * EP * 4;                    // per-wave patch: the y2 turn (32 rows x 144 B) and the epilogue
+  static constexpr int LDS = cmax(2 * BUF1, W2_OFF + 2 * BUF2);
+  static_assert(NPIX == 128 && NPIX1 % RPP1 == 0 && MID % RPP1 == 0 && MH == 64 && MID == NCP && NK1 % PD1 == 0 && NK2H % 6 == 0 && KT3 == 4, "layer2 shape");
+  static_assert(((NPIX1 + 31) / 32 + 1) / 2 == 3 && 6 * 32 <= XROWS + MID, "phase 1: 2 x 3 pixel tiles, the sixth one reads W1 rows of the stage");
+  static_assert(RPP1 % 16 == 0 && XROWS % 16 == 0, "the swizzle of a row is that of its thread (r1) / its lane (l32)");
+  static_assert(NW * PATCH <= ZERO_OFF && 32 * P2 == PATCH, "patches live in the dead y1 rows");
+  static_assert(LDS <= 80 * 1024, "two workgroups per CU");
+};
+
+template <int C, int MID, int IW, int TH>
+__global__ __launch_bounds__(256, 2) void bottleneck_halves_kernel(Params p) {
+  using K = CfgH<C, MID, IW, TH>;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6, l32 = lane & 31, h = lane >> 5;
+  const int tiles_img = p.H / TH, ntiles = p.B * tiles_img;
+  int T;
+  {   // the tile assignment of bottleneck_kernel: every XCD a contiguous run of tiles
+    const int b = (int)blockIdx.x, q = ntiles / 8, r = ntiles % 8, x = b % 8, s = b / 8;
+    T = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + s;
+  }
+  const int img = T / tiles_img, ty0 = (T - img * tiles_img) * TH;
+  SSG_BN_STAMP(0)
+
+  // phase-1 staging: thread = 16-byte piece ck1 of the 128-byte k-tile rows r1 + 32 u; waves = 2 rows of 3 pixel tiles x 2 pairs of
+  // channel tiles {j1b, j1b + 2}: every wave owns one channel tile of each y1 half
+  constexpr int RPP1 = K::RPP1, AU = K::XROWS / RPP1, WU = MID / RPP1, MT1 = K::NPIX1 / 32, MTW1 = 3;
+  const int ck1 = tid & 7, r1 = tid >> 3;
+  const float* ximg = p.x + (int64_t)img * p.H * IW * C;
+  const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(ximg), 0, (unsigned)(p.H * IW * C * 4), 0x00020000);
+  const int i1b = (wave >> 1) * MTW1, j1b = wave & 1;
+  v16f acc1[MTW1][2];                                        // [pixel tile][y1 half]
+#pragma unroll
+  for (int i = 0; i < MTW1; i++)
+#pragma unroll
+    for (int j = 0; j < 2; j++)
+#pragma unroll
+      for (int r = 0; r < 16; r++) acc1[i][j][r] = 0.f;
+  {
+    // =========================== phase 1: y1 = relu(conv1(x)) on the TH+2 halo rows, all MID channels ===========================
+    unsigned aoff[AU];
+#pragma unroll
+    for (int u = 0; u < AU; u++) {
+      const int pix = (ty0 - 1) * IW + r1 + RPP1 * u;        // rows above / below the image: out-of-range offset -> the load returns zeros
+      aoff[u] = (pix >= 0 && pix < p.H * IW) ? (unsigned)((pix * C + ck1 * 4) * 4) : 0x80000000u;
+    }
+    const float* w1p = p.w1 + (int64_t)r1 * C + ck1 * 4;
+    const int wsw = ((ck1 ^ ((r1 >> 1) & 7)) * 16), rsw = (l32 >> 1) & 7;   // swizzled chunk of this thread's stores / swizzle of this lane's rows
+    v4f sa[K::PD1][AU], sw[K::PD1][WU];
+#define SSG_BH_LOAD1(T_, S_)                                                                                         \
+    {                                                                                                                \
+      _Pragma("unroll") for (int u = 0; u < AU; u++) {                                                                \
+        const v4u raw = __builtin_amdgcn_raw_buffer_load_b128(xrsrc, aoff[u], (T_) * (K::K1T * 4), 0);                \
+        sa[S_][u] = __builtin_bit_cast(v4f, raw);                                                                   \
+      }                                                                                                               \
+      _Pragma("unroll") for (int u = 0; u < WU; u++) sw[S_][u] = *reinterpret_cast<const v4f*>(w1p + (int64_t)(RPP1 * u) * C + (T_) * K::K1T); \
+    }
+#define SSG_BH_STORE1(BUF_, S_)                                                                                      \
+    {                                                                                                                \
+      unsigned char* sb_ = smem + (BUF_) * K::BUF1;                                                                  \
+      _Pragma("unroll") for (int u = 0; u < AU; u++) *reinterpret_cast<v4f*>(sb_ + (r1 + RPP1 * u) * K::P1T + wsw) = sa[S_][u]; \
+      _Pragma("unroll") for (int u = 0; u < WU; u++) *reinterpret_cast<v4f*>(sb_ + (K::XROWS + r1 + RPP1 * u) * K::P1T + wsw) = sw[S_][u]; \
+    }
+    // (the sixth pixel tile of the second wave row does not exist: its fragment reads land in the W1 rows of the stage, its products
+    // are never written)
+#define SSG_BH_MMA1(BUF_)                                                                                            \
+    {                                                                                                                \
+      const unsigned char* sb_ = smem + (BUF_) * K::BUF1;                                                            \
+      _Pragma("unroll") for (int ks = 0; ks < 2; ks++) {                                                             \
+        const int ch_ = ((4 * ks + 2 * h) ^ rsw) * 16, cl_ = ((4 * ks + 2 * h + 1) ^ rsw) * 16;                      \
+        v8h xh_[MTW1], xl_[MTW1], wh_[2], wl_[2];                                                                    \
+        _Pragma("unroll") for (int i = 0; i < MTW1; i++) {                                                           \
+          const unsigned char* q_ = sb_ + ((i1b + i) * 32 + l32) * K::P1T;                                           \
+          xh_[i] = *reinterpret_cast<const v8h*>(q_ + ch_); xl_[i] = *reinterpret_cast<const v8h*>(q_ + cl_); }      \
+        _Pragma("unroll") for (int j = 0; j < 2; j++) {                                                              \
+          const unsigned char* q_ = sb_ + (K::XROWS + (j1b + 2 * j) * 32 + l32) * K::P1T;                            \
+          wh_[j] = *reinterpret_cast<const v8h*>(q_ + ch_); wl_[j] = *reinterpret_cast<const v8h*>(q_ + cl_); }      \
+        _Pragma("unroll") for (int i = 0; i < MTW1; i++) _Pragma("unroll") for (int j = 0; j < 2; j++)               \
+          acc1[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh_[j], xl_[i], acc1[i][j], 0, 0, 0);                  \
+        _Pragma("unroll") for (int i = 0; i < MTW1; i++) _Pragma("unroll") for (int j = 0; j < 2; j++)               \
+          acc1[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl_[j], xh_[i], acc1[i][j], 0, 0, 0);                  \
+        _Pragma("unroll") for (int i = 0; i < MTW1; i++) _Pragma("unroll") for (int j = 0; j < 2; j++)               \
+          acc1[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh_[j], xh_[i], acc1[i][j], 0, 0, 0);                  \
+      }                                                                                                              \
+    }
+    // k-tile KT_ sits in LDS buffer S_ and its register set S_ is free: fetch tile KT_ + 2 into it, multiply, pass tile KT_ + 1 on
+#define SSG_BH_STEP1(KT_, S_)                                                                                        \
+    {                                                                                                                \
+      if ((KT_) + K::PD1 < K::NK1) SSG_BH_LOAD1((KT_) + K::PD1, S_)                                                   \
+      SSG_BH_MMA1(S_)                                                                                                \
+      if ((KT_) + 1 < K::NK1) SSG_BH_STORE1(1 - (S_), 1 - (S_))                                                       \
+      __syncthreads();                                                                                               \
+    }
+    SSG_BH_LOAD1(0, 0) SSG_BH_LOAD1(1, 1)
+    SSG_BH_STORE1(0, 0)
+    __syncthreads();
+#pragma unroll 1
+    for (int kt0 = 0; kt0 < K::NK1; kt0 += 2) { SSG_BH_STEP1(kt0, 0) SSG_BH_STEP1(kt0 + 1, 1) }
+#undef SSG_BH_STEP1
+#undef SSG_BH_MMA1
+#undef SSG_BH_STORE1
+#undef SSG_BH_LOAD1
+  }
+  SSG_BN_STAMP(1)
+
+  // phase 2 / 3 staging: thread = 16-byte piece ck8 of the 128-byte stage rows r8 + 32 u; wave = its own 32 pixels x all channels
+  constexpr int RP8 = K::NTHR / 8, BU = MID / RP8;
+  const int ck8 = tid & 7, r8 = tid >> 3;
+  const float* w2p = p.w2 + (int64_t)r8 * (9 * MID) + ck8 * 4;
+  const int m2 = wave * 32 + l32, ty2 = m2 / IW, tx2 = m2 - ty2 * IW;    // this lane's output pixel (tile-local)
+  constexpr int NT2 = MID / 32;
+  v16f acc2[NT2];
+#pragma unroll
+  for (int j = 0; j < NT2; j++)
+#pragma unroll
+    for (int r = 0; r < 16; r++) acc2[j][r] = 0.f;
+  unsigned ovf = 0u;
+  v4f sb2[K::PD2][BU];
+#define SSG_BH_LOAD2(T_, S_)                                                                                         \
+  { _Pragma("unroll") for (int u = 0; u < BU; u++) sb2[S_][u] = *reinterpret_cast<const v4f*>(w2p + (int64_t)(RP8 * u) * (9 * MID) + (T_) * 32); }
+#define SSG_BH_STORE2(BUF_, S_)                                                                                      \
+  { unsigned char* sb_ = smem + K::W2_OFF + (BUF_) * K::BUF2;                                                        \
+    _Pragma("unroll") for (int u = 0; u < BU; u++) *reinterpret_cast<v4f*>(sb_ + (r8 + RP8 * u) * K::P2 + ck8 * 16) = sb2[S_][u]; }
+#define SSG_BH_STEP2(HF_, KT_, S_, B_)                                                                                \
+  {                                                                                                                  \
+    if ((KT_) + K::PD2 < K::NK2H) SSG_BH_LOAD2((HF_) * K::NK2H + (KT_) + K::PD2, S_)                                  \
+    {                                                                                                                \
+      const int cl = (KT_) / 9, tap = (KT_) - cl * 9, r = tap / 3, s = tap - r * 3;   /* cl: the chunk within the half */ \
+      const int xin = tx2 + s - 1;                                                                                   \
+      const int abase = (xin >= 0 && xin < IW) ? ((ty2 + r) * IW + xin) * K::PYH : K::ZERO_OFF;                      \
+      const unsigned char* wb = smem + K::W2_OFF + (B_) * K::BUF2 + l32 * K::P2 + h * 32;                             \
+      _Pragma("unroll") for (int ks = 0; ks < 2; ks++) {                                                             \
+        const unsigned char* q_ = smem + abase + (cl * 4 + ks * 2 + h) * 32;                                         \
+        const v8h xh_ = *reinterpret_cast<const v8h*>(q_), xl_ = *reinterpret_cast<const v8h*>(q_ + 16);             \
+        v8h wh_[NT2], wl_[NT2];                                                                                      \
+        _Pragma("unroll") for (int j = 0; j < NT2; j++) {                                                            \
+          wh_[j] = *reinterpret_cast<const v8h*>(wb + j * 32 * K::P2 + ks * 64);                                     \
+          wl_[j] = *reinterpret_cast<const v8h*>(wb + j * 32 * K::P2 + ks * 64 + 16); }                              \
+        _Pragma("unroll") for (int j = 0; j < NT2; j++) acc2[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh_[j], xl_, acc2[j], 0, 0, 0); \
+        _Pragma("unroll") for (int j = 0; j < NT2; j++) acc2[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl_[j], xh_, acc2[j], 0, 0, 0); \
+        _Pragma("unroll") for (int j = 0; j < NT2; j++) acc2[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh_[j], xh_, acc2[j], 0, 0, 0); \
+      }                                                                                                              \
+    }                                                                                                                \
+    if ((KT_) + 1 < K::NK2H) SSG_BH_STORE2((B_) ^ 1, ((S_) + 1) % K::PD2)                                             \
+    __syncthreads();                                                                                                 \
+  }
+  // One y1 half: its conv2 weights' first k-tiles on their way, the half's accumulators -> LDS (h8l8 pixel rows; rows outside the image
+  // are conv2's zero padding, not relu(bias)), then chunks 2 HF_, 2 HF_ + 1 of conv2 with the pixel operand from LDS.  The accumulators
+  // of half 1 stay parked in registers while half 0 multiplies; the barrier that ends half 0's last step frees the rows for them.
+  // Six steps per trip: the register set of step i is i % 3, its LDS buffer i & 1.
+#define SSG_BH_HALF(HF_)                                                                                             \
+  {                                                                                                                  \
+    SSG_BH_LOAD2((HF_) * K::NK2H, 0) SSG_BH_LOAD2((HF_) * K::NK2H + 1, 1) SSG_BH_LOAD2((HF_) * K::NK2H + 2, 2)        \
+    float4 cs1r[4], b1r[4];                                                                                          \
+    _Pragma("unroll") for (int q = 0; q < 4; q++) {                                                                  \
+      cs1r[q] = *reinterpret_cast<const float4*>(p.cs1 + (HF_) * K::MH + j1b * 32 + 8 * q + 4 * h);                  \
+      b1r[q] = *reinterpret_cast<const float4*>(p.b1 + (HF_) * K::MH + j1b * 32 + 8 * q + 4 * h); }                  \
+    _Pragma("unroll") for (int i = 0; i < MTW1; i++) {                                                               \
+      if (i1b + i >= MT1) continue;                           /* (the padding tile of the second wave row) */       \
+      const int hp0 = (i1b + i) * 32;                         /* first halo pixel of this MFMA tile */               \
+      const int irow = ty0 - 1 + (hp0 + l32) / IW;                                                                   \
+      const bool inside = irow >= 0 && irow < p.H;                                                                   \
+      _Pragma("unroll") for (int q = 0; q < 4; q++) {                                                                \
+        const int ch = j1b * 32 + 8 * q + 4 * h;              /* channel within the half */                          \
+        const float4 cs = cs1r[q], bi = b1r[q];                                                                      \
+        float4 v = make_float4(acc1[i][HF_][4 * q] * cs.x + bi.x, acc1[i][HF_][4 * q + 1] * cs.y + bi.y, acc1[i][HF_][4 * q + 2] * cs.z + bi.z, \
+                               acc1[i][HF_][4 * q + 3] * cs.w + bi.w);                                               \
+        v = relu4(v);                                                                                                \
+        if (!inside) v = make_float4(0.f, 0.f, 0.f, 0.f);                                                            \
+        uint2 hi, lo;                                                                                                \
+        encode4(v, hi, lo);                                                                                          \
+        ovf |= hi_nonfinite_bits(hi);                                                                                \
+        unsigned char* d = smem + (hp0 + l32) * K::PYH + (ch >> 3) * 32 + h * 8;                                     \
+        *reinterpret_cast<uint2*>(d) = hi; *reinterpret_cast<uint2*>(d + 16) = lo;                                   \
+      }                                                                                                              \
+    }                                                                                                                \
+    if ((HF_) == 0 && tid < K::PYH / 16) *reinterpret_cast<uint4*>(smem + K::ZERO_OFF + tid * 16) = make_uint4(0u, 0u, 0u, 0u);   /* (the phase-1 stages covered this row) */ \
+    SSG_BH_STORE2(0, 0)                                                                                              \
+    __syncthreads();                                                                                                 \
+    _Pragma("unroll 1") for (int kt0 = 0; kt0 < K::NK2H; kt0 += 6) {                                                 \
+      SSG_BH_STEP2(HF_, kt0, 0, 0) SSG_BH_STEP2(HF_, kt0 + 1, 1, 1) SSG_BH_STEP2(HF_, kt0 + 2, 2, 0)                  \
+      SSG_BH_STEP2(HF_, kt0 + 3, 0, 1) SSG_BH_STEP2(HF_, kt0 + 4, 1, 0) SSG_BH_STEP2(HF_, kt0 + 5, 2, 1)              \
+    }                                                                                                                \
+    SSG_BN_STAMP(2 + (HF_))                                                                                          \
+  }
+  SSG_BH_HALF(0)
+  SSG_BH_HALF(1)      // (its last barrier: every wave is past its last y1 / W2 read)
+#undef SSG_BH_HALF
+#undef SSG_BH_STEP2
+#undef SSG_BH_STORE2
+#undef SSG_BH_LOAD2
+
+  // ---- conv3 weights: stage s = (pass s / 4, 32-channel k-tile s % 4): rows of the pass's 128 output channels, 128 bytes each
+  constexpr int NS3 = K::NPASS * K::KT3;
+  const float* w3p = p.w3 + (int64_t)r8 * MID + ck8 * 4;
+  v4f sc3[2][BU];
+#define SSG_BH_LOAD3(T_, S_)                                                                                         \
+  { _Pragma("unroll") for (int u = 0; u < BU; u++)                                                                    \
+      sc3[S_][u] = *reinterpret_cast<const v4f*>(w3p + (int64_t)(((T_) / K::KT3) * K::NCP + RP8 * u) * MID + ((T_) % K::KT3) * 32); }
+#define SSG_BH_STORE3(BUF_, S_)                                                                                      \
+  { unsigned char* sb_ = smem + K::W2_OFF + (BUF_) * K::BUF2;                                                        \
+    _Pragma("unroll") for (int u = 0; u < BU; u++) *reinterpret_cast<v4f*>(sb_ + (r8 + RP8 * u) * K::P2 + ck8 * 16) = sc3[S_][u]; }
+  SSG_BH_LOAD3(0, 0)
+  SSG_BH_LOAD3(1, 1)
+
+  // ---- y2 -> MFMA fragments of conv3's pixel operand: each 32 x 32 accumulator tile through this wave's patch (in the dead y1 rows)
+  unsigned char* const patchb = smem + wave * K::PATCH;
+  v8h y2h[MID / 16], y2l[MID / 16];
+#pragma unroll
+  for (int j = 0; j < NT2; j++) {
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+      const float4 cs = *reinterpret_cast<const float4*>(p.cs2 + j * 32 + 8 * q + 4 * h), bi = *reinterpret_cast<const float4*>(p.b2 + j * 32 + 8 * q + 4 * h);
+      float4 v = make_float4(acc2[j][4 * q] * cs.x + bi.x, acc2[j][4 * q + 1] * cs.y + bi.y, acc2[j][4 * q + 2] * cs.z + bi.z, acc2[j][4 * q + 3] * cs.w + bi.w);
+      v = relu4(v);
+      uint2 hi, lo;
+      encode4(v, hi, lo);
+      ovf |= hi_nonfinite_bits(hi);
+      unsigned char* d = patchb + l32 * K::P2 + q * 32 + h * 8;
+      *reinterpret_cast<uint2*>(d) = hi; *reinterpret_cast<uint2*>(d + 16) = lo;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+#pragma unroll
+    for (int ks = 0; ks < 2; ks++) {
+      const unsigned char* q_ = patchb + l32 * K::P2 + (ks * 2 + h) * 32;
+      y2h[j * 2 + ks] = *reinterpret_cast<const v8h*>(q_); y2l[j * 2 + ks] = *reinterpret_cast<const v8h*>(q_ + 16);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  }
+  SSG_BH_STORE3(0, 0)
+  __syncthreads();
+  SSG_BN_STAMP(4)
+
+  // =========================== phase 3 + epilogue: out = relu(conv3(y2) + x), 128 output channels per pass ===========================
+  constexpr int EP = K::EP, CPR = 8, RPI = 8, ITS = 4, NT3 = K::NCP / 32;
+  const int chunk = lane % CPR, prow = lane / CPR, odd = lane & 1;
+  const int64_t gpix0 = ((int64_t)img * p.H + ty0) * IW + wave * 32;       // first output pixel of this wave (pixels are contiguous)
+  const float* __restrict__ resp = p.x + gpix0 * C;
+  float* __restrict__ outp = p.out + gpix0 * C;
+  float* const patch = reinterpret_cast<float*>(patchb);
+#if SSG_BN_NT_RES
+#define SSG_BH_RESLOAD(P_) ([&]() { const v4f t_ = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(P_)); return make_float4(t_[0], t_[1], t_[2], t_[3]); }())
+#else
+#define SSG_BH_RESLOAD(P_) (*reinterpret_cast<const float4*>(P_))
+#endif
+#pragma unroll 1
+  for (int ps = 0; ps < K::NPASS; ps++) {
+    const int cb3 = ps * NT3;
+    v16f acc3[NT3];
+#pragma unroll
+    for (int j = 0; j < NT3; j++)
+#pragma unroll
+      for (int r = 0; r < 16; r++) acc3[j][r] = 0.f;
+    float4 rr[2][ITS], b3r[2], cs3r[2];
+    // stage I_ of the pass sits in LDS buffer I_ & 1 and its register set is free: fetch two stages ahead, multiply, pass the next one on
+#define SSG_BH_STEP3(I_)                                                                                             \
+    {                                                                                                                \
+      const int s_ = ps * K::KT3 + (I_);                                                                             \
+      if (s_ + 2 < NS3) SSG_BH_LOAD3(s_ + 2, (I_) & 1)                                                                \
+      if constexpr ((I_) == K::KT3 - 1) {    /* the epilogue's first operands (two tiles ahead measures the same: the epilogue is VALU work) */ \
+        _Pragma("unroll") for (int it = 0; it < ITS; it++) rr[0][it] = SSG_BH_RESLOAD(resp + (int64_t)(it * RPI + prow) * C + cb3 * 32 + chunk * 4); \
+        b3r[0] = *reinterpret_cast<const float4*>(p.b3 + cb3 * 32 + chunk * 4); cs3r[0] = *reinterpret_cast<const float4*>(p.cs3 + cb3 * 32 + chunk * 4); \
+      }                                                                                                              \
+      const unsigned char* wb_ = smem + K::W2_OFF + ((I_) & 1) * K::BUF2 + l32 * K::P2 + h * 32;                      \
+      _Pragma("unroll") for (int ks = 0; ks < 2; ks++) {                                                             \
+        const v8h xh_ = y2h[(I_) * 2 + ks], xl_ = y2l[(I_) * 2 + ks];                                                \
+        v8h wh_[NT3], wl_[NT3];                                                                                      \
+        _Pragma("unroll") for (int j = 0; j < NT3; j++) {                                                            \
+          wh_[j] = *reinterpret_cast<const v8h*>(wb_ + j * 32 * K::P2 + ks * 64);                                    \
+          wl_[j] = *reinterpret_cast<const v8h*>(wb_ + j * 32 * K::P2 + ks * 64 + 16); }                             \
+        _Pragma("unroll") for (int j = 0; j < NT3; j++) acc3[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh_[j], xl_, acc3[j], 0, 0, 0); \
+        _Pragma("unroll") for (int j = 0; j < NT3; j++) acc3[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl_[j], xh_, acc3[j], 0, 0, 0); \
+        _Pragma("unroll") for (int j = 0; j < NT3; j++) acc3[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh_[j], xh_, acc3[j], 0, 0, 0); \
+      }                                                                                                              \
+      if (s_ + 1 < NS3) SSG_BH_STORE3(((I_) + 1) & 1, ((I_) + 1) & 1)                                                 \
+      __syncthreads();                                                                                               \
+    }
+    SSG_BH_STEP3(0) SSG_BH_STEP3(1) SSG_BH_STEP3(2) SSG_BH_STEP3(3)
+#undef SSG_BH_STEP3
+
+    // ---- epilogue of the pass: per channel tile a 32-pixel x 32-channel patch through LDS, then whole 128-byte row segments:
+    // bias, residual (x, h8l8), ReLU, re-encode, store.  The code path of bottleneck_kernel and conv.hip.
+#pragma unroll
+    for (int j = 0; j < NT3; j++) {
+      const int col = (cb3 + j) * 32 + chunk * 4;
+      if (j + 1 < NT3) {
+#pragma unroll
+        for (int it = 0; it < ITS; it++) rr[(j + 1) & 1][it] = SSG_BH_RESLOAD(resp + (int64_t)(it * RPI + prow) * C + col + 32);
+        b3r[(j + 1) & 1] = *reinterpret_cast<const float4*>(p.b3 + col + 32); cs3r[(j + 1) & 1] = *reinterpret_cast<const float4*>(p.cs3 + col + 32);
+      }
+      const float4 bias = b3r[j & 1], cs = cs3r[j & 1];
+#pragma unroll
+      for (int q = 0; q < 4; q++)
+        *reinterpret_cast<float4*>(patch + l32 * EP + 8 * q + 4 * h) = make_float4(acc3[j][4 * q], acc3[j][4 * q + 1], acc3[j][4 * q + 2], acc3[j][4 * q + 3]);
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+#pragma unroll
+      for (int it = 0; it < ITS; it++) {
+        const int pr = it * RPI + prow;
+        float4 v = *reinterpret_cast<const float4*>(patch + pr * EP + chunk * 4);
+        v.x = v.x * cs.x + bias.x; v.y = v.y * cs.y + bias.y; v.z = v.z * cs.z + bias.z; v.w = v.w * cs.w + bias.w;
+        const float4 rw = rr[j & 1][it];
+        float4 r4;
+        {   // even lane holds hi0..7 of the 8-channel group, odd lane lo0..7; each needs hi and lo of ITS four channels
+          const unsigned a0 = __float_as_uint(rw.x), a1 = __float_as_uint(rw.y), a2 = __float_as_uint(rw.z), a3 = __float_as_uint(rw.w);
+          const unsigned g0 = lane_xor1((odd ? a0 : a2)), g1 = lane_xor1((odd ? a1 : a3));
+          const unsigned h0 = odd ? g0 : a0, h1 = odd ? g1 : a1, l0 = odd ? a2 : g0, l1 = odd ? a3 : g1;
+          r4 = decode4(make_uint2(h0, h1), make_uint2(l0, l1));
+        }
+        v.x += r4.x; v.y += r4.y; v.z += r4.z; v.w += r4.w;
+        v = relu4(v);
+        uint2 hp, lp;
+        encode4(v, hp, lp);
+        ovf |= hi_nonfinite_bits(hp);
+        const unsigned rx = lane_xor1((odd ? hp.x : lp.x)), ry = lane_xor1((odd ? hp.y : lp.y));
+        const uint4 stv = make_uint4(odd ? rx : hp.x, odd ? ry : hp.y, odd ? lp.x : rx, odd ? lp.y : ry);
+#if SSG_BN_NT_STORE
+        { const v4u sv_ = {stv.x, stv.y, stv.z, stv.w}; __builtin_nontemporal_store(sv_, reinterpret_cast<v4u*>(outp + (int64_t)pr * C + col)); }
+#else
+        *reinterpret_cast<uint4*>(outp + (int64_t)pr * C + col) = stv;
+#endif
+      }
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    }
+  }
+#undef SSG_BH_RESLOAD
+#undef SSG_BH_STORE3
+#undef SSG_BH_LOAD3
+  if ((ovf & 0x80008000u) && p.overflow) *p.overflow = 1;
+  SSG_BN_STAMP(5)
+}
+
 }  // namespace bneck
 }  // namespace ssg
 
 // 1 when ssg_bottleneck_nhwc_x / ssg_bottleneck_ds_nhwc_x has a kernel for this block shape (CIN == C: identity block):
 //   layer1 of ResNet-50 at 256x128 input: H x 32 x 256, MID 64 (identity blocks and the first block, CIN = 64), 4-row tiles;
-//   layer2 identity blocks: H x 16 x 512, MID 128, 8-row tiles (one 8-wave workgroup per CU: the 128-channel halo intermediate is 85 KB)
+//   layer2 identity blocks: H x 16 x 512, MID 128, 8-row tiles (4 waves in channel halves, or 8 waves: SSG_BN_L2_WAVES)
 extern "C" int ssg_bottleneck_supported(int H, int W, int CIN, int C, int MID) {
   if (C == 256 && MID == 64 && (CIN == 256 || CIN == 64) && W == 32 && H > 0 && H % 4 == 0) return 1;
   if (C == 512 && MID == 128 && CIN == 512 && W == 16 && H > 0 && H % 8 == 0) return 1;
@@ -628,6 +987,25 @@ static int launch_bottleneck(const ssg::bneck::Params& p, hipStream_t stream) {
   return SSG_OK;
 }
 
+template <int C, int MID, int IW, int TH>
+static int launch_bottleneck_halves(const ssg::bneck::Params& p, hipStream_t stream) {
+  using namespace ssg::bneck;
+  using K = CfgH<C, MID, IW, TH>;
+  static bool attr_set = false;
+  if (!attr_set) {
+    SSG_HIP(hipFuncSetAttribute((const void*)bottleneck_halves_kernel<C, MID, IW, TH>, hipFuncAttributeMaxDynamicSharedMemorySize, K::LDS));
+    attr_set = true;
+  }
+  hipLaunchKernelGGL((bottleneck_halves_kernel<C, MID, IW, TH>), dim3(p.B * (p.H / TH)), dim3(K::NTHR), K::LDS, stream, p);
+  SSG_LAUNCH_CHECK("bottleneck_halves_kernel");
+  return SSG_OK;
+}
+
+// layer2 instance when SSG_BN_L2_WAVES is not set
+#ifndef SSG_BN_L2_WAVES_DEFAULT
+#define SSG_BN_L2_WAVES_DEFAULT 4
+#endif
+
 // Identity bottleneck block (no downsample branch, stride 1), split-half tensors:
 //   out = relu(conv3(relu(conv2(relu(conv1(x))))) + x),  x / out [B,H,W,C] h8l8, weights as ssg_conv2d_nhwc_x takes them
 //   (w1 [MID][C], w2 [MID][9*MID] in the k = (32-channel chunk, tap, channel) order, w3 [C][MID], each row pre-multiplied by a
@@ -644,7 +1022,14 @@ extern "C" int ssg_bottleneck_nhwc_x(const void* x, const void* w1, const float*
   p.x = (const float*)x; p.out = (float*)out;
   p.w1 = (const float*)w1; p.b1 = b1; p.cs1 = cs1; p.w2 = (const float*)w2; p.b2 = b2; p.cs2 = cs2; p.w3 = (const float*)w3; p.b3 = b3; p.cs3 = cs3;
   p.B = B; p.H = H; p.overflow = overflow;
-  if (C == 512) return launch_bottleneck<512, 128, 16, 8, 512, 8>(p, stream);
+  if (C == 512) {   // layer2: SSG_BN_L2_WAVES = 8 (one 8-wave workgroup per CU) or 4 (channel halves, two workgroups per CU), read per launch
+    const char* e = getenv("SSG_BN_L2_WAVES");
+    const int nw = e && *e ? atoi(e) : SSG_BN_L2_WAVES_DEFAULT;
+    if (nw == 4) return launch_bottleneck_halves<512, 128, 16, 8>(p, stream);
+    if (nw == 8) return launch_bottleneck<512, 128, 16, 8, 512, 8>(p, stream);
+    ssg_set_error("ssg_bottleneck_nhwc_x: SSG_BN_L2_WAVES=%s (4 or 8)", e);
+    return SSG_ERR_INVALID;
+  }
   return launch_bottleneck<256, 64, 32, 4, 256, 4>(p, stream);
 }
 

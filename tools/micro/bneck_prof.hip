@@ -1,6 +1,7 @@
 // Phase accounting of the fused bottleneck kernel (csrc/bottleneck.hip built with SSG_BN_PROF).
 // build + run on the GPU box:
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -DSSG_BN_PROF -I self-similarity-grouping_amd/csrc tools/micro/bneck_prof.hip -o /tmp/bneck_prof && /tmp/bneck_prof 512
+// -DBN_LAYER2: the 8-wave layer2 instance; -DBN_LAYER2 -DBN_L2H: the 4-wave channel-halves instance (bottleneck_halves_kernel)
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
@@ -37,12 +38,22 @@ int main(int argc, char** argv) {
   Params p;
   p.x = (const float*)x; p.out = (float*)out; p.w1 = (const float*)w1; p.b1 = bi; p.cs1 = cs; p.w2 = (const float*)w2; p.b2 = bi; p.cs2 = cs;
   p.w3 = (const float*)w3; p.b3 = bi; p.cs3 = cs; p.B = B; p.H = H; p.overflow = nullptr; p.prof = prof;
+#if defined(BN_LAYER2) && defined(BN_L2H)
+  using K = CfgH<KC, KMID, KIW, KTH>;
+  const auto kern = bottleneck_halves_kernel<KC, KMID, KIW, KTH>;
+  constexpr int NTHR = K::NTHR, NPH = 5;
+  const char* names[NPH] = {"phase 1 (conv1 loop)", "y1 half 0 + conv2 chunks 0-1", "y1 half 1 + conv2 chunks 2-3", "y2 turn + W3 prologue", "conv3 + epilogue, 4 passes"};
+#else
   using K = Cfg<KC, KMID, KIW, KTH, KC, KNW>;
-  hipFuncSetAttribute((const void*)bottleneck_kernel<KC, KMID, KIW, KTH, KC, KNW>, hipFuncAttributeMaxDynamicSharedMemorySize, K::LDS);
+  const auto kern = bottleneck_kernel<KC, KMID, KIW, KTH, KC, KNW>;
+  constexpr int NTHR = KNW * 64, NPH = 5;
+  const char* names[NPH] = {"phase 1 (conv1 loop)", "y1 write + W2 prologue", "phase 2 (conv2 loop)", "y2 write + phase 3 MMA", "epilogue (res + store)"};
+#endif
+  hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, K::LDS);
   hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
   for (int rep = 0; rep < 4; rep++) {
     hipEventRecord(e0);
-    hipLaunchKernelGGL((bottleneck_kernel<KC, KMID, KIW, KTH, KC, KNW>), dim3(ntiles), dim3(KNW * 64), K::LDS, 0, p);
+    hipLaunchKernelGGL(kern, dim3(ntiles), dim3(NTHR), K::LDS, 0, p);
     hipEventRecord(e1); hipEventSynchronize(e1);
     float ms; hipEventElapsedTime(&ms, e0, e1);
     printf("B=%d tiles=%d LDS=%d  %.3f ms  (%.2f TB/s x+out)\n", B, ntiles, K::LDS, ms, 2.0 * nx * 4 / ms / 1e9);
@@ -50,11 +61,10 @@ int main(int argc, char** argv) {
 #ifdef SSG_BN_PROF
   std::vector<unsigned long long> hp((size_t)ntiles * 8);
   hipMemcpy(hp.data(), prof, hp.size() * 8, hipMemcpyDeviceToHost);
-  const char* names[5] = {"phase 1 (conv1 loop)", "y1 write + W2 prologue", "phase 2 (conv2 loop)", "y2 write + phase 3 MMA", "epilogue (res + store)"};
-  double tot = 0, ph[5] = {0, 0, 0, 0, 0};
-  for (int t = 0; t < ntiles; t++) { for (int i = 0; i < 5; i++) ph[i] += (double)(hp[t * 8 + i + 1] - hp[t * 8 + i]); tot += (double)(hp[t * 8 + 5] - hp[t * 8]); }
-  for (int i = 0; i < 5; i++) printf("  %-26s %9.0f ticks/workgroup (%4.1f %%)\n", names[i], ph[i] / ntiles, 100.0 * ph[i] / tot);
-  printf("  %-26s %9.0f ticks/workgroup\n", "total", tot / ntiles);
+  double tot = 0, ph[NPH] = {};
+  for (int t = 0; t < ntiles; t++) { for (int i = 0; i < NPH; i++) ph[i] += (double)(hp[t * 8 + i + 1] - hp[t * 8 + i]); tot += (double)(hp[t * 8 + NPH] - hp[t * 8]); }
+  for (int i = 0; i < NPH; i++) printf("  %-28s %9.0f ticks/workgroup (%4.1f %%)\n", names[i], ph[i] / ntiles, 100.0 * ph[i] / tot);
+  printf("  %-28s %9.0f ticks/workgroup\n", "total", tot / ntiles);
 #endif
   return 0;
 }

@@ -53,7 +53,7 @@ def main():
     def conv_sum(rows):
         s, n, keep = 0.0, 0, []
         for r in rows:
-            if any(k in r for k in ("bottleneck_kernel", "conv_dma_kernel", "conv_igemm_kernel", "stem_pool_kernel")):
+            if any(k in r for k in ("bottleneck_kernel", "bottleneck_halves_kernel", "conv_dma_kernel", "conv_igemm_kernel", "stem_pool_kernel")):
                 parts = r.rsplit(",", 3)
                 s += float(parts[3]); n += int(parts[2]); keep.append(r)
         return s, n, keep
