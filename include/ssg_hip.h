@@ -346,6 +346,19 @@ int ssg_bottleneck_nhwc_x(const void* x, const void* w1, const float* b1, const 
 int ssg_bottleneck_ds_nhwc_x(const void* x, const void* w1, const float* b1, const float* cs1, const void* w2, const float* b2, const float* cs2,
                              const void* w3cat, const float* b3, const float* cs3, void* out, int B, int H, int W, int CIN, int C, int MID,
                              int32_t* overflow, ssg_stream_t stream);
+/* Next-conv instance of the layer1 identity block: the 1x1 convolution that opens the FOLLOWING block (layer2's entry conv1) rides in
+ * this block's epilogue, so its launch -- a read of all of `out` -- goes away.  ssg_bottleneck_attach_next stores a descriptor in a
+ * thread-local slot; this thread's next ssg_bottleneck_nhwc_x call consumes and clears it, whether it succeeds or not, and also writes
+ *   y1n [B,H,W,MIDN] = relu(conv1_next(out)): w1n [MIDN][C] h8l8 row-major, rows pre-multiplied by the powers of two cs1n undoes, b1n fp32;
+ *                      bit-identical to ssg_conv2d_nhwc_x(out, w1n, ...);
+ *   out_s2 [B,H/2,W/2,C] = out[:, ::2, ::2] (all a stride-2 downsample branch reads of `out`).
+ * y1n, out_s2 and that call's `out` may each be null (not written).  With a descriptor attached, a shape without
+ * ssg_bottleneck_next_supported (1 for H % 4 == 0, W 32, C 256, MID 64, MIDN 128) is SSG_ERR_INVALID, never a plain launch.
+ * ssg_bottleneck_next_enabled: the routing switch SSG_BN_L1_NEXT (0 | 1, read per call; unset: the library's compile-time default),
+ * SSG_ERR_INVALID for any other value. */
+int ssg_bottleneck_next_supported(int H, int W, int C, int MID, int MIDN);
+int ssg_bottleneck_next_enabled(void);
+int ssg_bottleneck_attach_next(const void* w1n, const float* b1n, const float* cs1n, void* y1n, void* out_s2, int MIDN);
 /* One identity BasicBlock of ResNet-18 / ResNet-34 (base.py:25-54 without a downsample branch, stride 1) in ONE launch, split-half
  * tensors: out = relu(conv2_3x3(relu(conv1_3x3(x) + b1)) + b2 + x).  x / out [B,H,W,C] h8l8 (out must not alias x); w1 / w2 [C][9*C]
  * (k = (32-channel chunk, tap, channel)) as ssg_conv2d_nhwc_x takes them, rows pre-multiplied by powers of two that cs1 / cs2 undo;

@@ -63,6 +63,10 @@ struct Params {
   int B, H;
   int* overflow;
   unsigned long long* prof = nullptr;   // SSG_BN_PROF builds: 8 phase timestamps (s_memtime) per workgroup
+  // next-conv instance (NXT): conv1 of the following block on the tile this block has just produced
+  const float* w1n = nullptr; const float* b1n = nullptr; const float* cs1n = nullptr;   // [MIDN][C] h8l8 row-major, rows pre-scaled by 1/cs1n
+  float* y1n = nullptr;                 // [B,H,IW,MIDN]
+  float* out_s2 = nullptr;              // [B,H/2,IW/2,C]: the pixels of `out` with even y and even x
 };
 #ifdef SSG_BN_PROF
 #define SSG_BN_STAMP(I_) { if (p.prof && threadIdx.x == 0) p.prof[(size_t)blockIdx.x * 8 + (I_)] = __builtin_readcyclecounter(); }
@@ -144,7 +148,7 @@ __device__ __forceinline__ void bn_dma16(const __amdgpu_buffer_rsrc_t r, unsigne
   __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)(uintptr_t)lds_addr, 16, voff, soff, 0, 0);
 }
 
-template <int C, int MID, int IW, int TH, int CIN, int NW>
+template <int C, int MID, int IW, int TH, int CIN, int NW, bool NXT = false>
 __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void bottleneck_kernel(Params p) {
   using K = Cfg<C, MID, IW, TH, CIN, NW>;
   constexpr bool DS = K::DS;
@@ -389,7 +393,8 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void bottleneck_kernel(Pa
 #pragma unroll
     for (int r = 0; r < 16; r++) acc2[j][r] = 0.f;
   const int m2 = pt2 * 32 + l32, ty2 = m2 / IW, tx2 = m2 - ty2 * IW;       // this lane's output pixel (tile-local)
-  float4 cs2r[NT2][4], b2r[NT2][4];                        // needed right after the loop
+  float4 cs2r[NT2][4], b2r[NT2][4];                        // needed right after the loop (NXT: fetched there, its registers do not reach)
+  if constexpr (!NXT)
 #pragma unroll
   for (int j = 0; j < NT2; j++)
 #pragma unroll
@@ -434,8 +439,201 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void bottleneck_kernel(Pa
 #undef SSG_BN_LOAD2
 #undef SSG_BN_STORE2
 
+  if constexpr (NXT) {
+  // =========================== next-conv instance: phase 3 in passes, then y1n = relu(conv1_next(out)) ===========================
+  // The last layer1 block also multiplies the tile it has just produced by conv1 of the next block (W1n [MIDN][C]), so that launch --
+  // a read of all of `out` from HBM -- goes away.  The wave keeps its y2 fragments in registers (K = 64: 32 of them); conv3 + epilogue
+  // run in passes of 64 output channels; the epilogue writes each encoded pair back in place of the 32 bytes it read from the
+  // wave's fp32 patch: at the 144-byte patch pitch that is the fragment format, and each 32-channel tile of `out` feeds two k-steps of
+  // acc4[4] += W1n . out (32 pixels x 128 channels per wave).  W3 stages (64 rows x 64 channels) and W1n stages (128 rows x 32
+  // channels) take turns in one two-buffer ring behind the wave rows: per pass W3, W1n, W1n; one barrier per stage.
+  // k-steps ascend, the three products keep their order: y1n is bit-identical to ssg_conv2d_nhwc_x(out, W1n).
+  static_assert(!DS && NW == 4 && MID == 64 && C == 256 && IW == 32 && NT2 == 2 && WC2 == 1, "the layer1 identity block");
+  constexpr int MIDN = 128, NCP = 64, NPASS = C / NCP, NSTEP = 3 * NPASS;
+  constexpr int P3N = MID * 4 + 16, PN = 144, NXSTG = cmax(NCP * P3N, MIDN * PN);   // stage rows: W3 256 B, W1n 128 B (pitch / 16 odd)
+  constexpr int EP = 36, CPR = 8, RPI = 8, ITS = 4;
+  static_assert(K::W3_OFF + 2 * NXSTG <= K::LDS && 32 * EP * 4 <= 32 * K::PY && EP * 4 == PN && NPASS % 2 == 0, "ring behind the wave rows, patch in them");
+  const int ck16 = tid & 15, r16 = tid >> 4, ckn = tid & 7, rn = tid >> 3;
+  // every global stream of this phase goes through a buffer resource: one 32-bit offset per lane and stream, the rest uniform (64-bit
+  // lane addresses per row of the epilogue do not fit next to acc4)
+  const __amdgpu_buffer_rsrc_t w3rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.w3), 0, (unsigned)(C * MID * 4), 0x00020000);
+  const __amdgpu_buffer_rsrc_t wnrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.w1n), 0, (unsigned)(MIDN * C * 4), 0x00020000);
+  const unsigned w3o = (unsigned)((r16 * MID + ck16 * 4) * 4), wno = (unsigned)((rn * C + ckn * 4) * 4);
+  v4f sn[2][4];
+#define SSG_BN_NLOAD(I_)      /* stage 6 pp + I_ -> register set I_ & 1 */                                           \
+  { if (6 * pp + (I_) < NSTEP) { const int ps_ = 2 * pp + (I_) / 3;                                                  \
+      if constexpr ((I_) % 3 == 0) { _Pragma("unroll") for (int u = 0; u < 4; u++) sn[(I_) & 1][u] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(w3rsrc, w3o, ((ps_ * NCP + 16 * u) * MID) * 4, 0)); } \
+      else { _Pragma("unroll") for (int u = 0; u < 4; u++) sn[(I_) & 1][u] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(wnrsrc, wno, ((32 * u) * C + (2 * ps_ + (I_) % 3 - 1) * 32) * 4, 0)); } } }
+#define SSG_BN_NSTORE(I_)     /* register set I_ & 1 -> LDS buffer I_ & 1 */                                         \
+  { if (6 * pp + (I_) < NSTEP) { unsigned char* sb_ = smem + K::W3_OFF + ((I_) & 1) * NXSTG;                         \
+      if constexpr ((I_) % 3 == 0) { _Pragma("unroll") for (int u = 0; u < 4; u++) *reinterpret_cast<v4f*>(sb_ + (r16 + 16 * u) * P3N + ck16 * 16) = sn[(I_) & 1][u]; } \
+      else { _Pragma("unroll") for (int u = 0; u < 4; u++) *reinterpret_cast<v4f*>(sb_ + (rn + 32 * u) * PN + ckn * 16) = sn[(I_) & 1][u]; } } }
+  { constexpr int pp = 0; SSG_BN_NLOAD(0) SSG_BN_NLOAD(1) }
+  // ---- y2 -> this wave's rows (as below), then its MFMA fragments for all of conv3: the rows are dead from here on
+  unsigned char* myrows = smem + (wave * 32) * K::PY;
+#pragma unroll
+  for (int j = 0; j < NT2; j++)
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+      const int ch = j * 32 + 8 * q + 4 * h;
+      const float4 cs = *reinterpret_cast<const float4*>(p.cs2 + ch), bi = *reinterpret_cast<const float4*>(p.b2 + ch);
+      float4 v = make_float4(acc2[j][4 * q] * cs.x + bi.x, acc2[j][4 * q + 1] * cs.y + bi.y, acc2[j][4 * q + 2] * cs.z + bi.z, acc2[j][4 * q + 3] * cs.w + bi.w);
+      v = relu4(v);
+      uint2 hi, lo;
+      encode4(v, hi, lo);
+      ovf |= hi_nonfinite_bits(hi);
+      unsigned char* d = myrows + l32 * K::PY + (ch >> 3) * 32 + h * 8;
+      *reinterpret_cast<uint2*>(d) = hi; *reinterpret_cast<uint2*>(d + 16) = lo;
+    }
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  v8h y2h[MID / 16], y2l[MID / 16];
+#pragma unroll
+  for (int ks = 0; ks < MID / 16; ks++) {
+    const unsigned char* q_ = myrows + l32 * K::PY + (ks * 2 + h) * 32;
+    y2h[ks] = *reinterpret_cast<const v8h*>(q_); y2l[ks] = *reinterpret_cast<const v8h*>(q_ + 16);
+  }
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  { constexpr int pp = 0; SSG_BN_NSTORE(0) }
+  __syncthreads();
+
+  const int chunk = lane % CPR, prow = lane / CPR, odd = lane & 1;
+  const int64_t gpix0 = ((int64_t)img * p.H + ty0) * IW + wave * 32;       // first output pixel of this wave: one image row
+  // x / out: the tile's 128 pixels are contiguous; this lane's rows are pixels wave * 32 + it * RPI + prow
+  const unsigned tpo = (unsigned)(((wave * 32 + prow) * C + chunk * 4) * 4);
+  const unsigned xro = (unsigned)(ty0 * IW * C * 4) + tpo;
+  const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(p.out ? p.out + ((int64_t)img * p.H + ty0) * IW * C : nullptr, 0,
+                                                                         p.out ? (unsigned)(K::NPIX * C * 4) : 0u, 0x00020000);
+  // out_s2: even image rows (ty0 is a multiple of 4: the even waves), even pixels of the row (pr even <=> prow even), whole 128-byte
+  // segments; the other lanes carry an out-of-range offset: their stores are dropped
+  const __amdgpu_buffer_rsrc_t srsrc = __builtin_amdgcn_make_buffer_rsrc(p.out_s2 ? p.out_s2 + (((int64_t)img * (p.H / 2) + ty0 / 2) * (IW / 2)) * C : nullptr, 0,
+                                                                         p.out_s2 ? (unsigned)((TH / 2) * (IW / 2) * C * 4) : 0u, 0x00020000);
+  const unsigned s2o = ((wave | prow) & 1) ? 0x80000000u : (unsigned)((((wave >> 1) * (IW / 2) + (prow >> 1)) * C + chunk * 4) * 4);
+  float* const patch = reinterpret_cast<float*>(myrows);
+  const unsigned char* const patchb = myrows;
+  v16f acc3[NCP / 32], acc4[MIDN / 32];
+#pragma unroll
+  for (int j = 0; j < MIDN / 32; j++)
+#pragma unroll
+    for (int r = 0; r < 16; r++) acc4[j][r] = 0.f;
+  float4 rr[ITS], b3r, cs3r;
+  constexpr int NT_RES = SSG_BN_NT_RES ? 2 : 0, NT_ST = SSG_BN_NT_STORE ? 2 : 0;   // cache-policy operand of the buffer instructions: nt
+  // the epilogue operands of channel tile T_ (residual rows, bias, scale): fetched as soon as the tile before has used its own (one
+  // register set: two leave no room for acc4), a multiply or more ahead of their use
+#define SSG_BN_NEPIOPS(T_)                                                                                           \
+  { _Pragma("unroll") for (int it = 0; it < ITS; it++) { const v4u t4_ = __builtin_amdgcn_raw_buffer_load_b128(xrsrc, xro, (it * RPI * C + (T_) * 32) * 4, NT_RES);  \
+      rr[it] = make_float4(__uint_as_float(t4_[0]), __uint_as_float(t4_[1]), __uint_as_float(t4_[2]), __uint_as_float(t4_[3])); } \
+    b3r = *reinterpret_cast<const float4*>(p.b3 + (T_) * 32 + chunk * 4); cs3r = *reinterpret_cast<const float4*>(p.cs3 + (T_) * 32 + chunk * 4); }
+  SSG_BN_NEPIOPS(0)
+  // stage I_ = W3 of pass 2 pp + I_ / 3: conv3 over the whole K = 64 for the pass's 64 output channels
+#define SSG_BN_NSTEP3(I_)                                                                                            \
+  { SSG_BN_NLOAD((I_) + 2)                                                                                         \
+    _Pragma("unroll") for (int j = 0; j < NCP / 32; j++) _Pragma("unroll") for (int r = 0; r < 16; r++) acc3[j][r] = 0.f; \
+    const unsigned char* wb_ = smem + K::W3_OFF + ((I_) & 1) * NXSTG + l32 * P3N + h * 32;                            \
+    _Pragma("unroll") for (int ks = 0; ks < MID / 16; ks++) {                                                        \
+      const v8h xh_ = y2h[ks], xl_ = y2l[ks];                                                                        \
+      v8h wh_[NCP / 32], wl_[NCP / 32];                                                                              \
+      _Pragma("unroll") for (int j = 0; j < NCP / 32; j++) {                                                         \
+        wh_[j] = *reinterpret_cast<const v8h*>(wb_ + j * 32 * P3N + ks * 64); wl_[j] = *reinterpret_cast<const v8h*>(wb_ + j * 32 * P3N + ks * 64 + 16); } \
+      _Pragma("unroll") for (int j = 0; j < NCP / 32; j++) acc3[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh_[j], xl_, acc3[j], 0, 0, 0); \
+      _Pragma("unroll") for (int j = 0; j < NCP / 32; j++) acc3[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl_[j], xh_, acc3[j], 0, 0, 0); \
+      _Pragma("unroll") for (int j = 0; j < NCP / 32; j++) acc3[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh_[j], xh_, acc3[j], 0, 0, 0); \
+    }                                                                                                                \
+    SSG_BN_NSTORE((I_) + 1)                                                                                          \
+    __syncthreads();                                                                                                 \
+  }
+  // stage I_ = W1n columns of out's channel tile ct_ = 2 ps_ + J_: the tile's epilogue (the code path of the plain instance; the encoded
+  // pair goes back in place of the fp32 values), then two k-steps of conv1_next from the patch
+#define SSG_BN_NSTEPN(I_, J_)                                                                                        \
+  { const int ct_ = 2 * (2 * pp + (I_) / 3) + (J_);                                                                 \
+    SSG_BN_NLOAD((I_) + 2)                                                                                           \
+    const float4 bias = b3r, cs = cs3r;                                                                              \
+    _Pragma("unroll") for (int q = 0; q < 4; q++)                                                                    \
+      *reinterpret_cast<float4*>(patch + l32 * EP + 8 * q + 4 * h) = make_float4(acc3[J_][4 * q], acc3[J_][4 * q + 1], acc3[J_][4 * q + 2], acc3[J_][4 * q + 3]); \
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");                                                           \
+    _Pragma("unroll") for (int it = 0; it < ITS; it++) {                                                             \
+      const int pr = it * RPI + prow;                                                                                \
+      float4 v = *reinterpret_cast<const float4*>(patch + pr * EP + chunk * 4);                                      \
+      v.x = v.x * cs.x + bias.x; v.y = v.y * cs.y + bias.y; v.z = v.z * cs.z + bias.z; v.w = v.w * cs.w + bias.w;    \
+      const float4 rw = rr[it];                                                                                      \
+      float4 r4;                                                                                                     \
+      {   /* even lane holds hi0..7 of the 8-channel group, odd lane lo0..7; each needs hi and lo of ITS four channels */ \
+        const unsigned a0 = __float_as_uint(rw.x), a1 = __float_as_uint(rw.y), a2 = __float_as_uint(rw.z), a3 = __float_as_uint(rw.w); \
+        const unsigned g0 = lane_xor1((odd ? a0 : a2)), g1 = lane_xor1((odd ? a1 : a3));                             \
+        const unsigned h0 = odd ? g0 : a0, h1 = odd ? g1 : a1, l0 = odd ? a2 : g0, l1 = odd ? a3 : g1;               \
+        r4 = decode4(make_uint2(h0, h1), make_uint2(l0, l1));                                                        \
+      }                                                                                                              \
+      v.x += r4.x; v.y += r4.y; v.z += r4.z; v.w += r4.w;                                                            \
+      v = relu4(v);                                                                                                  \
+      uint2 hp, lp;                                                                                                  \
+      encode4(v, hp, lp);                                                                                            \
+      ovf |= hi_nonfinite_bits(hp);                                                                                  \
+      const unsigned rx = lane_xor1((odd ? hp.x : lp.x)), ry = lane_xor1((odd ? hp.y : lp.y));                       \
+      const v4u sv_ = {odd ? rx : hp.x, odd ? ry : hp.y, odd ? lp.x : rx, odd ? lp.y : ry};                          \
+      *reinterpret_cast<v4u*>(patch + pr * EP + chunk * 4) = sv_;   /* lanes 2g, 2g + 1: hi x 8 | lo x 8 of channel group g */ \
+      if (p.out) __builtin_amdgcn_raw_buffer_store_b128(sv_, orsrc, tpo, (it * RPI * C + ct_ * 32) * 4, NT_ST);       \
+      if (p.out_s2) __builtin_amdgcn_raw_buffer_store_b128(sv_, srsrc, s2o, (it * (RPI / 2) * C + ct_ * 32) * 4, NT_ST); \
+    }                                                                                                                \
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");                                                           \
+    if (ct_ + 1 < C / 32) SSG_BN_NEPIOPS(ct_ + 1)                                                                    \
+    const unsigned char* wb_ = smem + K::W3_OFF + ((I_) & 1) * NXSTG + l32 * PN + h * 32;                             \
+    _Pragma("unroll") for (int ks = 0; ks < 2; ks++) {                                                               \
+      const unsigned char* q_ = patchb + l32 * PN + (ks * 2 + h) * 32;                                               \
+      const v8h xh_ = *reinterpret_cast<const v8h*>(q_), xl_ = *reinterpret_cast<const v8h*>(q_ + 16);               \
+      _Pragma("unroll") for (int jj = 0; jj < MIDN / 32; jj += 2) {   /* (pairs of channel tiles: registers) */     \
+        v8h wh_[2], wl_[2];                                                                                          \
+        _Pragma("unroll") for (int j = 0; j < 2; j++) {                                                              \
+          wh_[j] = *reinterpret_cast<const v8h*>(wb_ + (jj + j) * 32 * PN + ks * 64); wl_[j] = *reinterpret_cast<const v8h*>(wb_ + (jj + j) * 32 * PN + ks * 64 + 16); } \
+        _Pragma("unroll") for (int j = 0; j < 2; j++) acc4[jj + j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh_[j], xl_, acc4[jj + j], 0, 0, 0); \
+        _Pragma("unroll") for (int j = 0; j < 2; j++) acc4[jj + j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl_[j], xh_, acc4[jj + j], 0, 0, 0); \
+        _Pragma("unroll") for (int j = 0; j < 2; j++) acc4[jj + j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh_[j], xh_, acc4[jj + j], 0, 0, 0); \
+      }                                                                                                              \
+    }                                                                                                                \
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");                                                           \
+    SSG_BN_NSTORE((I_) + 1)                                                                                          \
+    __syncthreads();                                                                                                 \
+  }
+  // two passes per trip: the register set and the LDS buffer of step i are i & 1
+#pragma unroll 1
+  for (int pp = 0; pp < NPASS / 2; pp++) {
+    SSG_BN_NSTEP3(0) SSG_BN_NSTEPN(1, 0) SSG_BN_NSTEPN(2, 1)
+    SSG_BN_NSTEP3(3) SSG_BN_NSTEPN(4, 0) SSG_BN_NSTEPN(5, 1)
+  }
+  SSG_BN_STAMP(4)
+#undef SSG_BN_NSTEPN
+#undef SSG_BN_NSTEP3
+#undef SSG_BN_NEPIOPS
+#undef SSG_BN_NSTORE
+#undef SSG_BN_NLOAD
+  // ---- y1n: conv_dma_kernel's epilogue (scale, bias, ReLU, encode) per 32-channel tile through the patch; default cache policy: the
+  // next launch's operand
+  if (p.y1n) {
+    float* __restrict__ ynp = p.y1n + gpix0 * MIDN;
+#pragma unroll
+    for (int j = 0; j < MIDN / 32; j++) {
+      const int col = j * 32 + chunk * 4;
+      const float4 bias = *reinterpret_cast<const float4*>(p.b1n + col), cs = *reinterpret_cast<const float4*>(p.cs1n + col);
+#pragma unroll
+      for (int q = 0; q < 4; q++)
+        *reinterpret_cast<float4*>(patch + l32 * EP + 8 * q + 4 * h) = make_float4(acc4[j][4 * q], acc4[j][4 * q + 1], acc4[j][4 * q + 2], acc4[j][4 * q + 3]);
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+#pragma unroll
+      for (int it = 0; it < ITS; it++) {
+        const int pr = it * RPI + prow;
+        float4 v = *reinterpret_cast<const float4*>(patch + pr * EP + chunk * 4);
+        v.x = v.x * cs.x + bias.x; v.y = v.y * cs.y + bias.y; v.z = v.z * cs.z + bias.z; v.w = v.w * cs.w + bias.w;
+        v = relu4(v);
+        uint2 hp, lp;
+        encode4(v, hp, lp);
+        ovf |= hi_nonfinite_bits(hp);
+        const unsigned rx = lane_xor1((odd ? hp.x : lp.x)), ry = lane_xor1((odd ? hp.y : lp.y));
+        *reinterpret_cast<uint4*>(ynp + (int64_t)pr * MIDN + col) = make_uint4(odd ? rx : hp.x, odd ? ry : hp.y, odd ? lp.x : rx, odd ? lp.y : ry);
+      }
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    }
+  }
+  } else {
   // ---- conv3 weights: k-tiles 0 and 1 on their way while y2 is written (every wave is past its last y1 / W2 read)
-  constexpr int CU3 = C / RPP;                              // 16-byte pieces per thread and W3 k-tile (C rows x 64 B)
+  constexpr int CU3 = C / RPP;                             // 16-byte pieces per thread and W3 k-tile (C rows x 64 B)
   constexpr int K3 = MID + (DS ? CIN : 0);                 // conv3's reduction length (the weight row)
   const float* w3p = p.w3 + (int64_t)r0 * K3 + ck * 4;
   v4f sc3[2][CU3];
@@ -599,6 +797,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void bottleneck_kernel(Pa
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
   }
+  }   // (!NXT)
   if ((ovf & 0x80008000u) && p.overflow) *p.overflow = 1;
   SSG_BN_STAMP(5)
 }
@@ -973,16 +1172,16 @@ extern "C" int ssg_bottleneck_supported(int H, int W, int CIN, int C, int MID) {
   return 0;
 }
 
-template <int C, int MID, int IW, int TH, int CIN, int NW>
+template <int C, int MID, int IW, int TH, int CIN, int NW, bool NXT = false>
 static int launch_bottleneck(const ssg::bneck::Params& p, hipStream_t stream) {
   using namespace ssg::bneck;
   using K = Cfg<C, MID, IW, TH, CIN, NW>;
   static bool attr_set = false;
   if (!attr_set) {
-    SSG_HIP(hipFuncSetAttribute((const void*)bottleneck_kernel<C, MID, IW, TH, CIN, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, K::LDS));
+    SSG_HIP(hipFuncSetAttribute((const void*)bottleneck_kernel<C, MID, IW, TH, CIN, NW, NXT>, hipFuncAttributeMaxDynamicSharedMemorySize, K::LDS));
     attr_set = true;
   }
-  hipLaunchKernelGGL((bottleneck_kernel<C, MID, IW, TH, CIN, NW>), dim3(p.B * (p.H / TH)), dim3(NW * 64), K::LDS, stream, p);
+  hipLaunchKernelGGL((bottleneck_kernel<C, MID, IW, TH, CIN, NW, NXT>), dim3(p.B * (p.H / TH)), dim3(NW * 64), K::LDS, stream, p);
   SSG_LAUNCH_CHECK("bottleneck_kernel");
   return SSG_OK;
 }
@@ -1006,6 +1205,46 @@ static int launch_bottleneck_halves(const ssg::bneck::Params& p, hipStream_t str
 #define SSG_BN_L2_WAVES_DEFAULT 4
 #endif
 
+// Next-conv instance of the layer1 identity block: conv1 of the FOLLOWING block rides in this block's epilogue.
+// whether the embedder routes through it when SSG_BN_L1_NEXT is not set
+#ifndef SSG_BN_L1_NEXT_DEFAULT
+#define SSG_BN_L1_NEXT_DEFAULT 1
+#endif
+
+namespace {
+struct NextDesc { const float* w1n; const float* b1n; const float* cs1n; float* y1n; float* out_s2; int midn; bool set; };
+thread_local NextDesc g_next = {};   // attached by ssg_bottleneck_attach_next, consumed by this thread's next ssg_bottleneck_nhwc_x
+}
+
+// 1 when the last layer1 block (H x 32 x 256, MID 64, H % 4 == 0) can also compute a 256 -> MIDN = 128 1x1 convolution of its output
+extern "C" int ssg_bottleneck_next_supported(int H, int W, int C, int MID, int MIDN) {
+  return (H > 0 && H % 4 == 0 && W == 32 && C == 256 && MID == 64 && MIDN == 128) ? 1 : 0;
+}
+
+// SSG_BN_L1_NEXT (0 | 1, read per call; unset or empty: SSG_BN_L1_NEXT_DEFAULT): 1 when the embedder should take the fused route
+extern "C" int ssg_bottleneck_next_enabled(void) {
+  const char* e = getenv("SSG_BN_L1_NEXT");
+  if (!e || !*e) return SSG_BN_L1_NEXT_DEFAULT;
+  if ((e[0] == '0' || e[0] == '1') && !e[1]) return e[0] - '0';
+  ssg_set_error("SSG_BN_L1_NEXT=%s (0 or 1)", e);
+  return SSG_ERR_INVALID;
+}
+
+// Attach conv1 of the following block to this thread's next ssg_bottleneck_nhwc_x call, which then also writes
+//   y1n [B,H,W,MIDN] = relu(conv1_next(out)) (w1n [MIDN][C] h8l8 row-major, rows pre-scaled by 1/cs1n; bit-identical to ssg_conv2d_nhwc_x(out, ...))
+//   out_s2 [B,H/2,W/2,C] = out[:, ::2, ::2]
+// either may be null, and so may that call's `out`.  That call consumes the descriptor whether it succeeds or not; a shape without
+// ssg_bottleneck_next_supported is then an error, never a plain launch.
+extern "C" int ssg_bottleneck_attach_next(const void* w1n, const float* b1n, const float* cs1n, void* y1n, void* out_s2, int MIDN) {
+  g_next = NextDesc{};
+  if (!w1n || !b1n || !cs1n || MIDN != 128 || (y1n && y1n == out_s2)) {
+    ssg_set_error("ssg_bottleneck_attach_next: needs w1n, b1n, cs1n, MIDN = 128 and distinct outputs (MIDN=%d)", MIDN);
+    return SSG_ERR_INVALID;
+  }
+  g_next = NextDesc{(const float*)w1n, b1n, cs1n, (float*)y1n, (float*)out_s2, MIDN, true};
+  return SSG_OK;
+}
+
 // Identity bottleneck block (no downsample branch, stride 1), split-half tensors:
 //   out = relu(conv3(relu(conv2(relu(conv1(x))))) + x),  x / out [B,H,W,C] h8l8, weights as ssg_conv2d_nhwc_x takes them
 //   (w1 [MID][C], w2 [MID][9*MID] in the k = (32-channel chunk, tap, channel) order, w3 [C][MID], each row pre-multiplied by a
@@ -1014,14 +1253,25 @@ extern "C" int ssg_bottleneck_nhwc_x(const void* x, const void* w1, const float*
                                      const void* w3, const float* b3, const float* cs3, void* out, int B, int H, int W, int C, int MID,
                                      int32_t* overflow, hipStream_t stream) {
   using namespace ssg::bneck;
+  const NextDesc nd = g_next;
+  g_next = NextDesc{};
   if (B <= 0 || !ssg_bottleneck_supported(H, W, C, C, MID) || !cs1 || !cs2 || !cs3 || x == out) {
     ssg_set_error("ssg_bottleneck_nhwc_x: unsupported block B=%d H=%d W=%d C=%d MID=%d (see ssg_bottleneck_supported)", B, H, W, C, MID);
+    return SSG_ERR_INVALID;
+  }
+  if (nd.set && (!ssg_bottleneck_next_supported(H, W, C, MID, nd.midn) || x == nd.y1n || x == nd.out_s2 || (out && (out == nd.y1n || out == nd.out_s2)))) {
+    ssg_set_error("ssg_bottleneck_nhwc_x: no next-conv instance for B=%d H=%d W=%d C=%d MID=%d MIDN=%d with distinct tensors (see ssg_bottleneck_next_supported)",
+                  B, H, W, C, MID, nd.midn);
     return SSG_ERR_INVALID;
   }
   Params p;
   p.x = (const float*)x; p.out = (float*)out;
   p.w1 = (const float*)w1; p.b1 = b1; p.cs1 = cs1; p.w2 = (const float*)w2; p.b2 = b2; p.cs2 = cs2; p.w3 = (const float*)w3; p.b3 = b3; p.cs3 = cs3;
   p.B = B; p.H = H; p.overflow = overflow;
+  if (nd.set) {
+    p.w1n = nd.w1n; p.b1n = nd.b1n; p.cs1n = nd.cs1n; p.y1n = nd.y1n; p.out_s2 = nd.out_s2;
+    return launch_bottleneck<256, 64, 32, 4, 256, 4, true>(p, stream);
+  }
   if (C == 512) {   // layer2: SSG_BN_L2_WAVES = 8 (one 8-wave workgroup per CU) or 4 (channel halves, two workgroups per CU), read per launch
     const char* e = getenv("SSG_BN_L2_WAVES");
     const int nw = e && *e ? atoi(e) : SSG_BN_L2_WAVES_DEFAULT;

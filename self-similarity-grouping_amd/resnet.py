@@ -118,6 +118,14 @@ class _FoldedConv:
 _IN_SPLIT, _OUT_SPLIT, _W_TILED = 1, 2, 4      # include/ssg_hip.h SSG_CONV_IN_SPLIT / SSG_CONV_OUT_SPLIT / SSG_CONV_W_TILED
 
 
+def _next_enabled(L):
+    """SSG_BN_L1_NEXT as the library reads it (0 | 1, its own default when unset): layer2's entry conv1 rides in the last layer1 block"""
+    en = L.ssg_bottleneck_next_enabled()
+    if en < 0:
+        check(en, "ssg_bottleneck_next_enabled")
+    return en == 1
+
+
 def _attach_tiled(f):
     """f.wt: the k-tile-major copy of a split-half weight (ssg_conv_weights_tile) the LDS-DMA convolution launches stream their weight
     stages from, or None where there is no tiled form (stem, Cout % 128).  f.w moves into the first half of one buffer and the copy
@@ -464,26 +472,42 @@ class ResNet:
         return out
 
     @staticmethod
-    def _conv_dual(L, o, x, c3, ds, out_split=False, ovf=None, tiled=False):
-        """relu(conv3(o) + downsample(x)) as one GEMM (ssg_conv1x1_dual_nhwc_x)."""
+    def _conv_dual(L, o, x, c3, ds, out_split=False, ovf=None, tiled=False, stride2=None):
+        """relu(conv3(o) + downsample(x)) as one GEMM (ssg_conv1x1_dual_nhwc_x).  stride2: the sampling stride of x when it is not the
+        downsample branch's own (1: x holds only the pixels the branch reads, the out_s2 of _bottleneck's next-conv route)."""
         B, H, W, _ = o.shape
         _, H2, W2, _ = x.shape
         out = torch.empty((B, H, W, c3.cout), dtype=torch.float32, device=o.device)
         flags = (_IN_SPLIT if ds.split else 0) | (_OUT_SPLIT if out_split else 0) | (_W_TILED if tiled and ds.wt is not None else 0)
-        check(L.ssg_conv1x1_dual_nhwc_x(ptr(o), ptr(x), ptr(ds.w), ptr(ds.bias), ptr(out), B, H, W, c3.cin, H2, W2, ds.cin, ds.stride, c3.cout, 1,
+        check(L.ssg_conv1x1_dual_nhwc_x(ptr(o), ptr(x), ptr(ds.w), ptr(ds.bias), ptr(out), B, H, W, c3.cin, H2, W2, ds.cin,
+                                        ds.stride if stride2 is None else stride2, c3.cout, 1,
                                         flags, ds.acc_scale, ptr(getattr(ds, "cscale", None)), ptr(ovf), stream()), "ssg_conv1x1_dual_nhwc_x")
         return out
 
     @staticmethod
-    def _bottleneck(L, y, blk, ovf=None):
+    def _bottleneck(L, y, blk, ovf=None, nxt=None):
         """whole bottleneck block in one launch (ssg_bottleneck_nhwc_x / ssg_bottleneck_ds_nhwc_x); None when there is no fused
-        kernel for this block (stride-2 blocks, other shapes)"""
+        kernel for this block (stride-2 blocks, other shapes).  nxt: the following block.  When that one opens a stage (stride-2
+        conv2 and downsample branch), the kernel has a next-conv instance for the shapes and SSG_BN_L1_NEXT allows it, the launch
+        also runs nxt's conv1 and returns (y1n, out_s2) instead: relu(conv1_next(out)) and out[:, ::2, ::2], all nxt reads of out."""
         B, H, W, CIN = y.shape
         c1, c2, c3, ds = blk["c1"], blk["c2"], blk["c3"], blk["ds"]
         if os.environ.get("SSG_FUSED_BOTTLENECK", "1") == "0" or c2.stride != 1 or (ds is not None and ds.stride != 1):
             return None
         if not L.ssg_bottleneck_supported(H, W, CIN, c3.cout, c1.cout):
             return None
+        if ds is None and nxt is not None and nxt.get("kind") != "basic" and nxt["ds"] is not None:
+            n1, n2, nds = nxt["c1"], nxt["c2"], nxt["ds"]
+            if (n1.k == 1 and n1.stride == 1 and n1.split and n1.cscale is not None and n1.cin == c3.cout and n2.stride == 2 and nds.stride == 2
+                    and H % 2 == 0 and W % 2 == 0 and L.ssg_bottleneck_next_supported(H, W, c3.cout, c1.cout, n1.cout)
+                    and _next_enabled(L)):
+                y1n = torch.empty((B, H, W, n1.cout), dtype=torch.float32, device=y.device)
+                out_s2 = torch.empty((B, H // 2, W // 2, c3.cout), dtype=torch.float32, device=y.device)
+                check(L.ssg_bottleneck_attach_next(ptr(n1.w), ptr(n1.bias), ptr(n1.cscale), ptr(y1n), ptr(out_s2), n1.cout), "ssg_bottleneck_attach_next")
+                check(L.ssg_bottleneck_nhwc_x(ptr(y), ptr(c1.w), ptr(c1.bias), ptr(c1.cscale), ptr(c2.w), ptr(c2.bias), ptr(c2.cscale),
+                                              ptr(c3.w), ptr(c3.bias), ptr(c3.cscale), None, B, H, W, CIN, c1.cout, ptr(ovf), stream()),
+                      "ssg_bottleneck_nhwc_x")
+                return y1n, out_s2
         out = torch.empty((B, H, W, c3.cout), dtype=torch.float32, device=y.device)
         if ds is None:
             check(L.ssg_bottleneck_nhwc_x(ptr(y), ptr(c1.w), ptr(c1.bias), ptr(c1.cscale), ptr(c2.w), ptr(c2.bias), ptr(c2.cscale),
@@ -546,7 +570,7 @@ class ResNet:
         # SSG_CONV_PAIR=1 (round 6, experimental, off by default: measured in DESIGN.md section 11): conv3 + residual of an identity block and
         # conv1 of the next block as one launch (ssg_conv_pair_nhwc_x) where a kernel exists (layer3) and the tiles fill the chip
         pair = sp and os.environ.get("SSG_CONV_PAIR", "0") == "1"
-        blocks, o1_next = net["blocks"], None
+        blocks, o1_next, y_is_s2 = net["blocks"], None, False
         for bi, blk in enumerate(blocks):
             if hooks and bi in hooks:
                 hooks[bi]()
@@ -560,7 +584,10 @@ class ResNet:
                 y = self._conv(L, o, blk["c2"], res=r, relu=True, out_split=sp, ovf=ovf, tiled=tw)
                 continue
             if sp:
-                fused = self._bottleneck(L, y, blk, ovf)
+                fused = self._bottleneck(L, y, blk, ovf, nxt=blocks[bi + 1] if bi + 1 < len(blocks) else None)
+                if isinstance(fused, tuple):       # the next block's conv1 rode along: y is now out[:, ::2, ::2], all that block reads of it
+                    (o1_next, y), y_is_s2 = fused, True
+                    continue
                 if fused is not None:
                     y = fused
                     continue
@@ -568,7 +595,8 @@ class ResNet:
             o1_next = None
             o = self._conv(L, o, blk["c2"], out_split=sp, ovf=ovf, tiled=tw)
             if blk["ds"] is not None:
-                y = self._conv_dual(L, o, y, blk["c3"], blk["ds"], out_split=sp, ovf=ovf, tiled=tw)
+                y = self._conv_dual(L, o, y, blk["c3"], blk["ds"], out_split=sp, ovf=ovf, tiled=tw, stride2=1 if y_is_s2 else None)
+                y_is_s2 = False
                 continue
             nxt = blocks[bi + 1]["c1"] if bi + 1 < len(blocks) else None
             Bo, Ho, Wo, _ = o.shape

@@ -17,17 +17,25 @@ PEAK_TF, PEAK_GBS = 2516.6 / 3.0, 8000.0
 
 class Rec:
     def __init__(self, L):
-        self.L, self.rows, self.on = L, [], True
+        self.L, self.rows, self.on, self.next = L, [], True, None
 
     def __getattr__(self, k):
         fn = getattr(self.L, k)
-        if not self.on or not k.startswith("ssg_") or k.endswith("_supported") or k.endswith("_bytes") or k == "ssg_last_error":
+        if not self.on or not k.startswith("ssg_") or k.endswith("_supported") or k.endswith("_enabled") or k.endswith("_bytes") or k == "ssg_last_error":
             return fn
+        if k == "ssg_bottleneck_attach_next":      # no launch: the descriptor rides in the next ssg_bottleneck_nhwc_x, whose row carries it
+            def attach(*a):
+                self.next = a
+                return fn(*a)
+            return attach
 
         def timed(*a):
             e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
             e0.record(); rc = fn(*a); e1.record()
-            self.rows.append((k, a, e0, e1))
+            if k == "ssg_bottleneck_nhwc_x" and self.next is not None:
+                self.rows.append((k + "+next", a + self.next, e0, e1)); self.next = None
+            else:
+                self.rows.append((k, a, e0, e1))
             return rc
         return timed
 
@@ -56,6 +64,14 @@ def work(name, a, B):
         flop = 2.0 * B_ * H * W * (C * MID + 9 * MID * MID + MID * C)
         byt = 4.0 * (2 * B_ * H * W * C + C * MID + 9 * MID * MID + MID * C)
         return flop, byt, "bottleneck %dx%d C=%d mid=%d" % (H, W, C, MID)
+    if name == "ssg_bottleneck_nhwc_x+next":     # the block plus conv1 of the next one (ssg_bottleneck_attach_next's arguments follow the block's)
+        B_, H, W, C, MID = [v(x) for x in a[11:16]]
+        out, y1n, out_s2, MIDN = v(a[10]), v(a[21]), v(a[22]), v(a[23])
+        flop = 2.0 * B_ * H * W * (C * MID + 9 * MID * MID + MID * C + C * MIDN)
+        px = B_ * H * W
+        byt = 4.0 * (px * C + (px * C if out else 0) + (px * MIDN if y1n else 0) + (px // 4 * C if out_s2 else 0)
+                     + C * MID + 9 * MID * MID + MID * C + C * MIDN)
+        return flop, byt, "bottleneck %dx%d C=%d mid=%d + next conv1 ->%d%s" % (H, W, C, MID, MIDN, "" if out else ", out_s2 only")
     if name == "ssg_bottleneck_ds_nhwc_x":
         B_, H, W, CIN, C, MID = [v(x) for x in a[11:17]]
         flop = 2.0 * B_ * H * W * (CIN * MID + 9 * MID * MID + (MID + CIN) * C)

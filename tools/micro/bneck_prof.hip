@@ -2,6 +2,7 @@
 // build + run on the GPU box:
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -DSSG_BN_PROF -I self-similarity-grouping_amd/csrc tools/micro/bneck_prof.hip -o /tmp/bneck_prof && /tmp/bneck_prof 512
 // -DBN_LAYER2: the 8-wave layer2 instance; -DBN_LAYER2 -DBN_L2H: the 4-wave channel-halves instance (bottleneck_halves_kernel)
+// -DBN_L1NEXT: the next-conv instance of the layer1 block as the embedder launches it (y1n and out_s2 written, out not)
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
@@ -38,7 +39,18 @@ int main(int argc, char** argv) {
   Params p;
   p.x = (const float*)x; p.out = (float*)out; p.w1 = (const float*)w1; p.b1 = bi; p.cs1 = cs; p.w2 = (const float*)w2; p.b2 = bi; p.cs2 = cs;
   p.w3 = (const float*)w3; p.b3 = bi; p.cs3 = cs; p.B = B; p.H = H; p.overflow = nullptr; p.prof = prof;
-#if defined(BN_LAYER2) && defined(BN_L2H)
+#if defined(BN_L1NEXT) && !defined(BN_LAYER2)
+  std::vector<uint16_t> hwn((size_t)128 * C * 2);
+  fill_halves(hwn, 5, 6, 6);
+  void *wn, *y1n, *os2;
+  hipMalloc(&wn, hwn.size() * 2); hipMalloc(&y1n, (size_t)B * H * W * 128 * 4); hipMalloc(&os2, nx);
+  hipMemcpy(wn, hwn.data(), hwn.size() * 2, hipMemcpyHostToDevice);
+  p.out = nullptr; p.w1n = (const float*)wn; p.b1n = bi; p.cs1n = cs; p.y1n = (float*)y1n; p.out_s2 = (float*)os2;
+  using K = Cfg<KC, KMID, KIW, KTH, KC, KNW>;
+  const auto kern = bottleneck_kernel<KC, KMID, KIW, KTH, KC, KNW, true>;
+  constexpr int NTHR = KNW * 64, NPH = 5;
+  const char* names[NPH] = {"phase 1 (conv1 loop)", "y1 write + W2 prologue", "phase 2 (conv2 loop)", "y2 turn + conv3 | epilogue | conv1_next passes", "y1n epilogue"};
+#elif defined(BN_LAYER2) && defined(BN_L2H)
   using K = CfgH<KC, KMID, KIW, KTH>;
   const auto kern = bottleneck_halves_kernel<KC, KMID, KIW, KTH>;
   constexpr int NTHR = K::NTHR, NPH = 5;

@@ -5,8 +5,9 @@ import json
 import sys
 
 
-def algorithmic_bytes(B):
-    """every launch's input + output + residual + weights once, 4 bytes per value, for the current launch set"""
+def algorithmic_bytes(B, l1_next=True):
+    """every launch's input + output + residual + weights once, 4 bytes per value, for the current launch set.  l1_next: layer2's entry
+    conv1 rides in the last layer1 block (SSG_BN_L1_NEXT=1), which writes y1n and the stride-2 quarter of its output instead of the output"""
     def t(h, w, c):
         return B * h * w * c * 4
     tot = [0, 0]
@@ -15,21 +16,25 @@ def algorithmic_bytes(B):
         tot[0] += b; tot[1] += 1
     add(B * 3 * 256 * 128 * 4 + t(64, 32, 64) + 64 * 224 * 4)                                   # stem + maxpool
     add(t(64, 32, 64) + t(64, 32, 256) + (64 * 64 + 64 * 576 + 256 * 128) * 4)                   # layer1 block 1 (fused)
-    for _ in (2, 3):
-        add(2 * t(64, 32, 256) + (64 * 256 + 64 * 576 + 256 * 64) * 4)                           # layer1 identity blocks (fused)
+    add(2 * t(64, 32, 256) + (64 * 256 + 64 * 576 + 256 * 64) * 4)                               # layer1 identity blocks (fused)
+    if l1_next:
+        add(t(64, 32, 256) + t(64, 32, 128) + t(32, 16, 256) + (64 * 256 + 64 * 576 + 256 * 64 + 128 * 256) * 4)
+    else:
+        add(2 * t(64, 32, 256) + (64 * 256 + 64 * 576 + 256 * 64) * 4)
 
-    def block(h, w, cin, mid, stride, ds, fused=False):
+    def block(h, w, cin, mid, stride, ds, fused=False, c1_done=False):
         oh, ow = h // stride, w // stride
         if fused:
             add(2 * t(h, w, cin) + (cin * mid + 9 * mid * mid + mid * 4 * mid) * 4)
             return
-        add(t(h, w, cin) + t(h, w, mid) + cin * mid * 4)
+        if not c1_done:
+            add(t(h, w, cin) + t(h, w, mid) + cin * mid * 4)
         add(t(h, w, mid) + t(oh, ow, mid) + 9 * mid * mid * 4)
         if ds:
             add(t(oh, ow, mid) + t(oh, ow, cin) + t(oh, ow, 4 * mid) + (mid + cin) * 4 * mid * 4)
         else:
             add(t(oh, ow, mid) + 2 * t(oh, ow, 4 * mid) + mid * 4 * mid * 4)
-    block(64, 32, 256, 128, 2, True)
+    block(64, 32, 256, 128, 2, True, c1_done=l1_next)
     for _ in (2, 3, 4):
         block(32, 16, 512, 128, 1, False, fused=True)
     block(32, 16, 512, 256, 2, True)
@@ -59,7 +64,7 @@ def main():
         return s, n, keep
     fs, fn, fk = conv_sum(sec["FETCH_SIZE"]); ws, wn, wk = conv_sum(sec["WRITE_SIZE"])
     fetch, write = fs * 1024 * 2 / 4, ws * 1024 / 4
-    alg, nl = algorithmic_bytes(B)
+    alg, nl = algorithmic_bytes(B, l1_next=(fn // 4 == algorithmic_bytes(B, True)[1]))
     sys.path.insert(0, __import__("os").path.dirname(__import__("os").path.dirname(__import__("os").path.abspath(__file__))))
     from bench import build_fingerprint, embed_fingerprint
     js = {"source": "profiles/%s.md" % __import__("os").path.basename(out), "build": build_fingerprint(), "embed_build": embed_fingerprint(), "batch": B, "launches_per_forward": fn // 4, "fetch_bytes_per_forward": fetch,
