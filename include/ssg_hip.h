@@ -966,6 +966,26 @@ int ssg_inc_maxpool_nhwc_x(const void* in, void* out, int B, int H, int W, int C
 int ssg_inc_avgpool3_nhwc_x(const void* in, void* out, int B, int H, int W, int C, int split, int out_ld, ssg_stream_t stream);
 int ssg_inc_head_finish(const float* x, float* out, int rows, int C, int mode, ssg_stream_t stream);
 
+/* ---- OPTICS on a precomputed distance matrix (ssg_amd.optics.OPTICS; csrc/optics.hip) ------------------------------------------------
+ * sklearn 1.7.2's compute_optics_graph(metric='precomputed') with its bits.  The matrix is a view as above -- mode 0 (M = J' half,
+ * v, lambda_value), mode 1 (half) or mode 2 (float64) -- always the whole N x N matrix of one GPU, widened to float64 element by element.
+ * around15(x) = rint(x * 1e15) / 1e15 with the three roundings apart (np.around(x, 15); +inf stays +inf).
+ * ssg_optics_core_dist: core[i] = around15(c > max_eps ? +inf : c), c = the min_samples-th smallest entry of row i with the diagonal
+ *   entry counted as it stands; exact for every min_samples in [2, N] (one wave per row, radix select over order-preserving keys).
+ * ssg_optics_order: the ordering loop in ONE workgroup.  Step t: p = the unprocessed index of smallest reachability (ties and all-inf:
+ *   the smallest index), ordering[t] = p; when core[p] is finite every unprocessed j with X[p,j] <= max_eps takes
+ *   r = around15(max(X[p,j], core[p])) and predecessor[j] = p when r < reachability[j].  ordering, predecessor [N] int64 (predecessor
+ *   starts at -1), reachability [N] float64 (starts at +inf).  state: where the loop keeps the reachabilities of the unprocessed points --
+ *   1 = LDS (N <= ssg_optics_lds_max_n()), 2 = global memory (ws: N * 8 bytes, 8-byte aligned), 0 = LDS when it fits, else global.
+ *   No synchronisation between workgroups, no spin loop, no atomic: every loop is bounded by N.
+ * Refused with SSG_ERR_INVALID before any device call: a null pointer, N < 2, min_samples outside [2, N], mode 0 without v, a negative
+ *   or NaN max_eps, a state outside 0..2, state 1 with N too large, the global state without its workspace. */
+int ssg_optics_lds_max_n(void);
+int ssg_optics_core_dist(const void* M, const uint16_t* v, int N, int mode, double lambda_value, int min_samples, double max_eps, double* core,
+                         ssg_stream_t stream);
+int ssg_optics_order(const void* M, const uint16_t* v, int N, int mode, double lambda_value, const double* core, double max_eps, int state,
+                     void* ws, size_t ws_bytes, int64_t* ordering, double* reachability, int64_t* predecessor, ssg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -892,3 +892,7 @@ class AffinityPropagation:
 
     def fit_predict(self, X, y=None, *, stages=None):
         return self.fit(X, stages=stages).labels_
+
+
+# OPTICS (ssg_amd/optics.py: the ordering on the device, the eps and xi cuts on the host) is part of this module's surface
+from .optics import OPTICS, cluster_optics_dbscan, cluster_optics_xi, compute_optics_graph  # noqa: E402,F401

@@ -138,6 +138,35 @@ def generate_selflabel_affinity(e_dist, r_dist, n_iter, args, cluster_list=[]): 
     return labels_list, cluster_list
 
 
+def generate_selflabel_optics(e_dist, r_dist, n_iter, args, cluster_list=[]):   # noqa: B006 (mutable default kept: reference :280)
+    """selftraining.py:280-313 with OPTICS in the place of the eps rule + DBSCAN: a density clustering that does not stake the run on one
+    eps.  The estimator is created at iteration 0 and cached in `cluster_list`; `args` needs `.no_rerank` and may carry `.optics_method`
+    ('xi': labels with no eps at all; 'dbscan': the eps cut of the ordering), `.optics_xi` (0.05), `.optics_min_samples` (4) and
+    `.optics_max_eps` (inf).  With 'dbscan', eps is the reference's rho rule (`cluster.eps_rule(dist, args.rho)`) at iteration 0, printed
+    with the reference's line and frozen on the cached estimator like selftraining.py:283-298.  One GPU only."""
+    from .optics import OPTICS
+    labels_list = []
+    for s in range(len(r_dist)):
+        tmp_dist = e_dist[s] if args.no_rerank else r_dist[s]
+        if n_iter == 0:
+            method = getattr(args, "optics_method", "xi")
+            eps = None
+            if method == "dbscan":
+                eps = float(eps_rule(tmp_dist, args.rho)[0])
+                print('eps in cluster: {:.3f}'.format(eps))
+            cluster = OPTICS(metric='precomputed', cluster_method=method, eps=eps, xi=getattr(args, "optics_xi", 0.05),
+                             min_samples=getattr(args, "optics_min_samples", 4), max_eps=getattr(args, "optics_max_eps", np.inf))
+            cluster_list.append(cluster)
+        else:
+            cluster = cluster_list[s]
+        print('Clustering and labeling...')
+        labels = cluster.fit_predict(tmp_dist)
+        num_ids = len(set(labels[labels >= 0].tolist()))
+        print('Iteration {} have {} training ids'.format(n_iter + 1, num_ids))
+        labels_list.append(labels)
+    return labels_list, cluster_list
+
+
 def select_labeled(labels_list):
     """selftraining.py:315-324 join: keep sample i iff no split labelled it -1.
     Returns (kept indices, [per-split label lists])."""
