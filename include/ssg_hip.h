@@ -986,6 +986,31 @@ int ssg_optics_core_dist(const void* M, const uint16_t* v, int N, int mode, doub
 int ssg_optics_order(const void* M, const uint16_t* v, int N, int mode, double lambda_value, const double* core, double max_eps, int state,
                      void* ws, size_t ws_bytes, int64_t* ordering, double* reachability, int64_t* predecessor, ssg_stream_t stream);
 
+/* ---- HDBSCAN on a precomputed distance matrix (ssg_amd.hdbscan.HDBSCAN; csrc/hdbscan.hip) ---------------------------------------------
+ * The matrix stages of sklearn 1.7.2's HDBSCAN(metric='precomputed') with their bits.  The matrix is a view as above -- mode 0 (M = J'
+ * half, v, lambda_value), mode 1 (half) or mode 2 (float64) -- always the whole N x N matrix of one GPU, widened to float64 element by
+ * element; nothing N x N is written.
+ * ssg_hdbscan_check: one pass over the matrix.  counts[0] = the entries that are NaN; counts[1] = the ordered pairs (i, j), the
+ *   diagonal included, that fail np.isclose(X[i,j], X[j,i], rtol=1e-7, atol=1e-9): |x - y| <= 1e-9 + 1e-7 |y| with y finite, or x == y
+ *   (two equal infinities are close, an infinity against a finite value is not).  counts: two int64 words, zeroed by the call.
+ * ssg_hdbscan_core_dist: core[i] = c / alpha, c = the min_samples-th smallest entry of row i with the diagonal entry counted as it
+ *   stands; exact for every min_samples in [1, N] (the radix select of ssg_optics_core_dist).
+ * ssg_hdbscan_mst: Prim from node 0 in ONE workgroup, N - 1 steps.  m[j] starts at +inf.  Step t with current node c: every node j
+ *   outside the tree takes m[j] = min(m[j], max(core[c], core[j], X[c,j] / alpha)); new = the node outside the tree of smallest m (ties
+ *   and all-inf: the smallest index); current[t] = c (the node the step started from, NOT the node that gave `new` its minimum),
+ *   next[t] = new, distance[t] = m[new]; then c = new.  current, next [N - 1] int64, distance [N - 1] float64, in Prim order.  The
+ *   matrix must hold no NaN (ssg_hdbscan_check counts them).  state: where the loop keeps m -- 1 = LDS (N <= ssg_hdbscan_lds_max_n()),
+ *   2 = global memory (ws: N * 8 bytes, 8-byte aligned), 0 = LDS when it fits, else global; every placement gives the same bits.
+ *   No synchronisation between workgroups, no spin loop, no atomic: every loop is bounded by N.
+ * Refused with SSG_ERR_INVALID before any device call: a null or misaligned pointer, N < 2, min_samples outside [1, N], mode 0 without v,
+ *   an alpha that is not positive and finite, a state outside 0..2, state 1 with N too large, the global state without its workspace. */
+int ssg_hdbscan_lds_max_n(void);
+int ssg_hdbscan_check(const void* M, const uint16_t* v, int N, int mode, double lambda_value, int64_t* counts, ssg_stream_t stream);
+int ssg_hdbscan_core_dist(const void* M, const uint16_t* v, int N, int mode, double lambda_value, int min_samples, double alpha, double* core,
+                          ssg_stream_t stream);
+int ssg_hdbscan_mst(const void* M, const uint16_t* v, int N, int mode, double lambda_value, const double* core, double alpha, int state,
+                    void* ws, size_t ws_bytes, int64_t* current, int64_t* next, double* distance, ssg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

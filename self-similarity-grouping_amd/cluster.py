@@ -896,3 +896,5 @@ class AffinityPropagation:
 
 # OPTICS (ssg_amd/optics.py: the ordering on the device, the eps and xi cuts on the host) is part of this module's surface
 from .optics import OPTICS, cluster_optics_dbscan, cluster_optics_xi, compute_optics_graph  # noqa: E402,F401
+# HDBSCAN (ssg_amd/hdbscan.py: the check, the core distances and the spanning tree on the device, the tree stages on the host) likewise
+from .hdbscan import HDBSCAN  # noqa: E402,F401

@@ -12,7 +12,7 @@
 // workgroup reduction.  There is no synchronisation between workgroups, no spin loop and no atomic: every loop below is bounded by N.
 // The state is one double per point -- its reachability while it is unprocessed, NaN once it is processed (a reachability is never NaN:
 // an entry that is NaN fails `<= max_eps` and is skipped) -- in LDS while 8 N bytes fit, else in a workspace in global memory.
-#include "matview.h"
+#include "kth_select.h"
 
 namespace ssg {
 
@@ -52,59 +52,17 @@ __device__ __forceinline__ double optics_unkey(uint64_t k) {
 }
 // ------------------------------------------------------------------ end of the scalar rules
 
-// One wave per row: radix select of the k-th smallest key, eight 8-bit digits from the top, one stream of the row per digit.  The four
-// waves of a workgroup walk the same number of rows (a wave past the end repeats the last row and writes nothing), so the barriers match.
+// One wave per row: the min_samples-th smallest entry by the radix select of kth_select.h.  The four waves of a workgroup walk the same
+// number of rows (a wave past the end repeats the last row and writes nothing), so the barriers match.
 template <int MODE>
 __global__ __launch_bounds__(256) void optics_core_kernel(MatView mv, int k, double max_eps, double* __restrict__ core) {
   __shared__ int hist[4][256];
   const int lane = lane_id(), wave = (int)(threadIdx.x >> 6);
-  int* h = hist[wave];
   for (int base = (int)blockIdx.x * 4; base < mv.nrows; base += (int)gridDim.x * 4) {
     const bool live = base + wave < mv.nrows;
     const int il = live ? base + wave : mv.nrows - 1;
-    const int gi = mv.row0 + il;
-    RowStream rs(il, mv.N, mv.nrows);
-    uint64_t prefix = 0;      // the digits chosen so far
-    int want = k;             // 1-based rank among the keys that carry the prefix
-    for (int shift = 56; shift >= 0; shift -= 8) {
-      for (int b = lane; b < 256; b += 64) h[b] = 0;
-      __syncthreads();
-      for (int c = 0; c < rs.nchunks; c++) {
-        double d[8];
-        load_vals<MODE>(mv, rs, c, lane, gi, d);
-        const int j0 = rs.col0(c, lane);
-#pragma unroll
-        for (int e = 0; e < 8; e++) {
-          const int j = j0 + e;
-          if (j < 0 || j >= mv.N) continue;
-          const uint64_t key = optics_key(d[e]);
-          if (shift == 56 || (key >> (shift + 8)) == prefix) atomicAdd(&h[(int)((key >> shift) & 255u)], 1);
-        }
-      }
-      __syncthreads();
-      int c4[4], tot = 0;
-#pragma unroll
-      for (int q = 0; q < 4; q++) { c4[q] = h[lane * 4 + q]; tot += c4[q]; }
-      int inc = tot;
-#pragma unroll
-      for (int s = 1; s < 64; s <<= 1) { const int o = __shfl_up(inc, s, 64); if (lane >= s) inc += o; }
-      int below = inc - tot, digit = lane * 4 + 3;
-      const bool mine = below < want && want <= inc;       // exactly one lane: the counts add up to at least `want`
-      bool found = !mine;
-#pragma unroll
-      for (int q = 0; q < 3; q++) {
-        if (found) continue;
-        if (want <= below + c4[q]) { digit = lane * 4 + q; found = true; }
-        else below += c4[q];
-      }
-      const uint64_t m = __ballot(mine);
-      const int src = m ? __ffsll((long long)m) - 1 : 0;
-      digit = __shfl(digit, src, 64); below = __shfl(below, src, 64);
-      prefix = (prefix << 8) | (uint64_t)digit;
-      want -= below;
-      __syncthreads();
-    }
-    if (live && lane == 0) core[il] = optics_core_finish(optics_unkey(prefix), max_eps);
+    const double kth = row_kth_smallest<MODE>(mv, il, k, hist[wave]);
+    if (live && lane == 0) core[il] = optics_core_finish(kth, max_eps);
   }
 }
 

@@ -167,6 +167,32 @@ def generate_selflabel_optics(e_dist, r_dist, n_iter, args, cluster_list=[]):   
     return labels_list, cluster_list
 
 
+def generate_selflabel_hdbscan(e_dist, r_dist, n_iter, args, cluster_list=[]):   # noqa: B006 (mutable default kept: reference :280)
+    """selftraining.py:280-313 with HDBSCAN in the place of the eps rule + DBSCAN: labels with no eps, and a per-sample
+    `probabilities_` on the cached estimator that a fine-tune phase can use as a weight.  The estimator is created at iteration 0 and
+    cached in `cluster_list`; `args` needs `.no_rerank` and may carry `.hdbscan_min_cluster_size` (4, the reference's DBSCAN min_samples),
+    `.hdbscan_min_samples` (None: min_cluster_size), `.hdbscan_method` ('eom'), `.hdbscan_epsilon` (0.0) and
+    `.hdbscan_allow_single_cluster` (False).  One GPU only."""
+    from .hdbscan import HDBSCAN
+    labels_list = []
+    for s in range(len(r_dist)):
+        tmp_dist = e_dist[s] if args.no_rerank else r_dist[s]
+        if n_iter == 0:
+            cluster = HDBSCAN(metric='precomputed', min_cluster_size=getattr(args, "hdbscan_min_cluster_size", 4),
+                              min_samples=getattr(args, "hdbscan_min_samples", None), cluster_selection_method=getattr(args, "hdbscan_method", "eom"),
+                              cluster_selection_epsilon=getattr(args, "hdbscan_epsilon", 0.0),
+                              allow_single_cluster=getattr(args, "hdbscan_allow_single_cluster", False))
+            cluster_list.append(cluster)
+        else:
+            cluster = cluster_list[s]
+        print('Clustering and labeling...')
+        labels = cluster.fit_predict(tmp_dist)
+        num_ids = len(set(labels[labels >= 0].tolist()))
+        print('Iteration {} have {} training ids'.format(n_iter + 1, num_ids))
+        labels_list.append(labels)
+    return labels_list, cluster_list
+
+
 def select_labeled(labels_list):
     """selftraining.py:315-324 join: keep sample i iff no split labelled it -1.
     Returns (kept indices, [per-split label lists])."""
