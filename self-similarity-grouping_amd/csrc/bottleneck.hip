@@ -22,30 +22,17 @@
 // downsample 1x1 convolution rides in conv3's reduction (K = MID + CIN, weights concatenated, as ssg_conv1x1_dual_nhwc_x does)
 // and replaces the residual; its pixel operand (this wave's 32 pixels x CIN channels) is loaded straight into MFMA fragments.
 //
-// Layer1 (C = 256, MID = 64, 32-pixel rows, TH = 4): 4 waves, 2 workgroups per CU (<= 80 KB of LDS each) -- one's loads run under
-// the other's multiplies.  Layer2 (C = 512, MID = 128, 16-pixel rows, TH = 8) has two instances: bottleneck_halves_kernel below (4 waves,
-// y1 in channel halves, 2 workgroups per CU: the default) and the 8-wave one of this kernel (SSG_BN_L2_WAVES=8): the 128-channel halo
-// intermediate alone is 85 KB, so ONE 8-wave workgroup per CU (150 KB): phase 2 = 4 pixel tiles x 2 channel groups, phase 3 = a wave pair per pixel tile, the
-// epilogue patches take over the dead W3 stages; its phases are serial on a CU (measured 0.75 -> 0.62 ms per block).
+// Both kernels here are 4-wave workgroups of 128 output pixels in <= 80 KB of LDS, two per CU: one's loads, stores and epilogue
+// arithmetic run under the other's multiplies.  bottleneck_kernel is layer1 (C = 256, MID = 64, 32-pixel rows, TH = 4: the identity
+// block, the DS variant and the next-conv instance); bottleneck_halves_kernel below is layer2 (C = 512, MID = 128,
+// 16-pixel rows, TH = 8), whose 128-channel halo intermediate (85 KB) only fits in channel halves.
 // All operand tiles are staged global -> registers -> LDS with the loads several k-tiles ahead (register rings), one barrier per
 // stage:
-//   phase 1  y1[(TH+2)*IW, MID] = relu(x W1^T)   k-tiles of 16 channels: x rows (64 B each) + W1 rows; wave = 3 x 1 MFMA tiles
+//   phase 1  y1[(TH+2)*IW, MID] = relu(x W1^T)   k-tiles of 32 channels: x rows (whole 128-byte lines) + W1 rows; wave = 3 x 1 MFMA tiles
 //   phase 2  y2[TH*IW, MID]     = relu(conv3x3(y1))   k-tiles = (32-channel chunk, tap): W2 rows (128 B); wave = 32 pixels x MID
 //   phase 3  out[TH*IW, C]      = relu(y2 W3^T + x)   k-tiles of 16 channels: W3 rows; wave = its own 32 pixels x all C channels
 #include "ssg_common.h"
 #include <cstdlib>
-
-// Round 6: cache policy of the block's two streams that nobody re-reads from the L2 -- the stores of `out` (1-2 GB per launch at B = 1000)
-// and the residual re-read of x (its last use).  With the default policy both allocate lines in the 4 MB L2s that the x rows, the halo
-// rows of the neighbouring workgroup and the weights go through; with `nt` the layer1 identity blocks run 1.48 -> 1.30-1.35 ms and the
-// layer2 ones 1.22 -> 1.12 ms at nearly the same fabric traffic (FETCH_SIZE - 3 %: profiles/r06_ab_nt_policy.txt).  Same values, same
-// order: bit-identical.
-#ifndef SSG_BN_NT_STORE
-#define SSG_BN_NT_STORE 1
-#endif
-#ifndef SSG_BN_NT_RES
-#define SSG_BN_NT_RES 1
-#endif
 
 namespace ssg {
 namespace bneck {
@@ -76,24 +63,17 @@ struct Params {
 
 constexpr int cmax(int a, int b) { return a > b ? a : b; }
 
-template <int C, int MID, int IW, int TH, int CIN = C, int NW = 4>
+template <int C, int MID, int IW, int TH, int CIN = C>
 struct Cfg {
-  static constexpr int HROWS = TH + 2, NPIX1 = HROWS * IW, NPIX = TH * IW;
-  static constexpr int NTHR = NW * 64, RPP = NTHR / 4;  // 64-byte k-tile rows staged per pass of the workgroup (phase 3)
-  // phase-1 k-tiles: 16 channels (64-byte row pieces) or, for the 8-wave layer2 kernel, 32 channels (whole 128-byte lines, half the
-  // load -> LDS -> barrier -> fragment round trips: a step costs ~1250 cycles in those round trips alone, whatever it multiplies)
-#ifndef SSG_BN_K1T
-#define SSG_BN_K1T 32
-#endif
-#ifndef SSG_BN_K1T4
-#define SSG_BN_K1T4 32               // round 4: whole 128-byte lines per pixel row and k-tile for the 4-wave layer1 kernel too (16: 64-byte pieces,
-#endif                               // two texture-addresser line accesses per useful line): identity blocks 1.59 -> 1.53 ms, bit-identical
-  static constexpr int K1T = NW == 8 ? SSG_BN_K1T : SSG_BN_K1T4, KS1 = K1T / 16, CPR1 = 4 * KS1, RPP1 = NTHR / CPR1;
+  static constexpr int NW = 4, NTHR = NW * 64, HROWS = TH + 2, NPIX1 = HROWS * IW, NPIX = TH * IW;
+  static constexpr int RPP = NTHR / 4;                 // 64-byte k-tile rows staged per pass of the workgroup (phase 3)
+  // phase-1 k-tiles: 32 channels, whole 128-byte lines per pixel row (16-channel tiles, 64-byte pieces, cost two texture-addresser line
+  // accesses per useful line and twice the load -> LDS -> barrier -> fragment round trips: identity blocks 1.59 -> 1.53 ms)
+  static constexpr int K1T = 32, KS1 = K1T / 16, CPR1 = 4 * KS1, RPP1 = NTHR / CPR1;
   static constexpr int XROWS = (NPIX1 + RPP1 - 1) / RPP1 * RPP1;   // x rows of a phase-1 stage, padded to whole passes (the padding loads return zeros)
   static constexpr int P1 = 80;                        // LDS pitch of a 64-byte k-tile row (pitch/16 odd: conflict-free b128)
-  static constexpr int P1T = K1T * 4 + 16;             // ... of a phase-1 row (80 or 144 bytes)
-  static constexpr int KT2 = NW == 8 ? 2 : 1;          // 32-channel (chunk, tap) k-tiles of conv2 per LDS stage: the 8-wave workgroup (alone on its CU) halves its barriers
-  static constexpr int P2 = KT2 * 128 + 16;            // ... of a phase-2 stage row (KT2 x 128 bytes of a W2 row)
+  static constexpr int P1T = K1T * 4 + 16;             // ... of a phase-1 row (144 bytes)
+  static constexpr int P2 = 128 + 16;                  // ... of a phase-2 stage row (one (chunk, tap) k-tile: 128 bytes of a W2 row)
   static constexpr int PY = MID * 4 + 16;              // ... of a y1 / y2 pixel row (all MID channels, h8l8)
   static constexpr int BUF1 = (XROWS + MID) * P1T;     // phase-1 stage: x rows, then W1 rows
   static constexpr int ZERO_OFF = NPIX1 * PY;          // one all-zero pixel row (conv2's left / right padding)
@@ -101,20 +81,13 @@ struct Cfg {
   static constexpr int W3_OFF = (NPIX * PY + 255) / 256 * 256, BUF3 = C * P1;
   static constexpr int LDS = cmax(cmax(2 * BUF1, W2_OFF + 2 * BUF2), W3_OFF + 2 * BUF3);
   static constexpr int DS = CIN != C;                  // downsample variant: conv3's reduction is [y2 | x]
-#ifdef SSG_BN_ABL_NK1                                  // ablation builds (tools/micro/bneck_prof.hip): a shortened conv1 reduction, wrong results
-  static constexpr int NK1 = SSG_BN_ABL_NK1;
-#else
-  static constexpr int NK1 = CIN / K1T;
-#endif
-  static constexpr int NK2 = (MID / 32) * 9 / KT2, NK3 = (MID + (DS ? CIN : 0)) / 16;
-  // stages of global loads in flight ahead of the multiply (PD1 = 4 measures the same: phase 1 is bound by HBM bandwidth, not latency)
-  static constexpr int PD1MAX = K1T == 64 ? 2 : (K1T == 32 ? 4 : 8);
-  static constexpr int PD1 = NK1 < PD1MAX ? NK1 : PD1MAX, PD2 = KT2 == 1 ? 6 : 3;
-  static_assert(((MID / 32) * 9) % KT2 == 0 && NK2 % PD2 == 0, "phase-2 stages and ring");
-  static_assert((NW == 4 || NW == 8) && NPIX == 128 && NPIX1 % 32 == 0 && MID % RPP == 0 && MID % RPP1 == 0 && C % RPP == 0 && MID % (NW * 8) == 0, "128 output pixels, whole staging passes");
-  static constexpr bool ZERO_EARLY = 2 * BUF1 <= ZERO_OFF;   // the zero row is written while phase 1 runs -- unless the (32-channel) stages cover it
-  static_assert(LDS <= (NW == 4 ? 80 : 160) * 1024, "4 waves: two workgroups per CU; 8 waves: one");
-  static_assert(NW == 4 || NW * 32 * 36 * 4 <= 2 * BUF3, "8 waves: the epilogue patches take over the W3 stages");
+  static constexpr int NK1 = CIN / K1T, NK2 = (MID / 32) * 9, NK3 = (MID + (DS ? CIN : 0)) / 16;
+  // stages of global loads in flight ahead of the multiply (phase 1 is bound by HBM bandwidth, not latency: four are enough)
+  static constexpr int PD1 = NK1 < 4 ? NK1 : 4, PD2 = 6;
+  static_assert(NK2 % PD2 == 0, "phase-2 ring");
+  static_assert(NPIX == 128 && NPIX1 % 32 == 0 && MID % RPP == 0 && MID % RPP1 == 0 && C % RPP == 0 && MID % (NW * 8) == 0, "128 output pixels, whole staging passes");
+  static constexpr bool ZERO_EARLY = 2 * BUF1 <= ZERO_OFF;   // the zero row is written while phase 1 runs -- unless the stages cover it
+  static_assert(LDS <= 80 * 1024, "two workgroups per CU");
 };
 
 __device__ __forceinline__ unsigned pack2(_Float16 a, _Float16 b) {
@@ -141,16 +114,25 @@ __device__ __forceinline__ float4 relu4(float4 v) {
 // x*w = xh*wl + xl*wh + xh*wh (the order of conv.hip's split_mma_step), weights as the first MFMA operand:
 // C/D layout col = lane&31 -> pixel, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5) -> channel
 
-// one LDS-DMA instruction: 64 lanes x 16 bytes, global (buffer resource, per-lane byte offset + uniform offset) -> LDS at `lds_addr` +
-// 16 * lane.  A function of its own: with the builtin called directly from the kernel template (per-lane offset from a local array) the
-// HOST pass of hipcc drops the kernel's launch stub without a diagnostic (undefined __device_stub__ at load time).
-__device__ __forceinline__ void bn_dma16(const __amdgpu_buffer_rsrc_t r, unsigned lds_addr, unsigned voff, int soff) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)(uintptr_t)lds_addr, 16, voff, soff, 0, 0);
+// Cache policy of the block's two streams that nobody re-reads from the L2 -- the residual re-read of x (its last use) and the stores of
+// `out` (1-2 GB per launch at B = 1000).  With the default policy both allocate lines in the 4 MB L2s that the x rows, the halo rows of
+// the neighbouring workgroup and the weights go through; with `nt` the layer1 identity blocks run 1.48 -> 1.30-1.35 ms and the layer2
+// ones 1.22 -> 1.12 ms at nearly the same fabric traffic (FETCH_SIZE - 3 %: profiles/r06_ab_nt_policy.txt).  Same values, same order.
+template <int C>
+__device__ __forceinline__ float4 load_res_nt(const float* res, int row, int col) {   // channels col .. col + 3 of pixel row `row` of res [.][C]
+  const v4f t = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(res + (int64_t)row * C + col));
+  return make_float4(t[0], t[1], t[2], t[3]);
 }
+__device__ __forceinline__ void store_out_nt(float* dst, const uint4 v) {
+  const v4u sv = {v.x, v.y, v.z, v.w};
+  __builtin_nontemporal_store(sv, reinterpret_cast<v4u*>(dst));
+}
+constexpr int AUX_NT = 2;   // the same policy as the cache-policy operand of a buffer instruction (the next-conv instance's streams)
 
-template <int C, int MID, int IW, int TH, int CIN, int NW, bool NXT = false>
-__global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void bottleneck_kernel(Params p) {
-  using K = Cfg<C, MID, IW, TH, CIN, NW>;
+template <int C, int MID, int IW, int TH, int CIN, bool NXT = false>
+__global__ __launch_bounds__(256, 2) void bottleneck_kernel(Params p) {
+  using K = Cfg<C, MID, IW, TH, CIN>;
+  constexpr int NW = K::NW;
   constexpr bool DS = K::DS;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6, l32 = lane & 31, h = lane >> 5;
@@ -167,7 +149,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void bottleneck_kernel(Pa
   // =========================== phase 1: y1 = relu(conv1(x)) on the TH+2 halo rows ===========================
   constexpr int RPP = K::RPP, RPP1 = K::RPP1, AU = K::XROWS / RPP1, WU = MID / RPP1;   // 16-byte pieces per thread and k-tile: x rows, W1 rows
   const int ck = tid & 3, r0 = tid >> 2;               // phase 3 staging (64-byte rows)
-  const int ck1 = tid % K::CPR1, r1 = tid / K::CPR1;   // phase 1 staging (64- or 128-byte rows)
+  const int ck1 = tid % K::CPR1, r1 = tid / K::CPR1;   // phase 1 staging (128-byte rows)
   const float* ximg = p.x + (int64_t)img * p.H * IW * CIN;
   const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(ximg), 0, (unsigned)(p.H * IW * CIN * 4), 0x00020000);
   // MFMA tiles of phase 1: (NPIX1/32) pixel tiles x (MID/32) channel tiles over the waves
@@ -192,84 +174,6 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void bottleneck_kernel(Pa
     for (int q = 0; q < 4; q++) {
       cs1r[j][q] = *reinterpret_cast<const float4*>(p.cs1 + (j1b + j) * 32 + 8 * q + 4 * h); b1r[j][q] = *reinterpret_cast<const float4*>(p.b1 + (j1b + j) * 32 + 8 * q + 4 * h);
     }
-#ifndef SSG_BN_P1DMA
-#define SSG_BN_P1DMA 1
-#endif
-  if constexpr (NW == 8 && K::K1T == 32 && SSG_BN_P1DMA) {
-    // ---- 8-wave kernel: LDS-DMA stages + register double-buffered fragments.  One workgroup per CU: with register-staged stages every
-    // wave stores, waits at the barrier, reads its fragments and multiplies at the same time as the other seven -- per 32-channel k-tile
-    // 1350 cycles of LDS traffic and 1150 cycles of MFMA one after the other (measured 3000).  Here the x rows and W1 rows go
-    // global -> LDS directly (buffer_load ... lds; rows of 128 bytes, 16-byte chunks XOR-swizzled with (row >> 1) & 7 on the global side
-    // and in the fragment reads: conflict-free b128 reads), four 36 KB stages with three k-tiles in flight (the y1 / W2 regions are not
-    // live yet), and the fragments of k-tile t + 1 are read into a second register set right after the barrier that publishes them,
-    // under the second k-step of tile t.  Same products in the same order: bit-identical.
-    constexpr int NS = 4, XR = K::NPIX1, SROWS = XR + MID, STG = SROWS * 128, NBLK = SROWS / 8, TDMA = (NBLK + NW - 1) / NW;
-    static_assert(K::NK1 % NS == 0 && NS * STG <= K::LDS && SROWS % 8 == 0 && XR % 8 == 0 && MTW1 == 3 && NTW1 == 1, "phase-1 DMA stages");
-    const int wv = __builtin_amdgcn_readfirstlane(wave);
-    const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.w1), 0, (unsigned)(MID * CIN * 4), 0x00020000);
-    unsigned go[TDMA];                                       // per DMA instruction of this wave: global byte offset of its lane's 16-byte chunk in k-tile 0
-    int gblk[TDMA];                                          // ... and its 8-row block of the stage (wave-uniform); blocks < XR / 8 hold x rows
-#pragma unroll
-    for (int u = 0; u < TDMA; u++) {
-      int blk = wv + NW * u;
-      if (blk >= NBLK) blk = wv;                             // (36 blocks over 8 waves: the last four waves fetch their first block twice -- keeps vmcnt uniform)
-      gblk[u] = blk;
-      const int r = blk * 8 + (lane >> 3), lc = (lane & 7) ^ ((r >> 1) & 7);
-      if (blk < XR / 8) {
-        const int pix = (ty0 - 1) * IW + r;                  // rows above / below the image: out-of-range offset -> zeros
-        go[u] = (pix >= 0 && pix < p.H * IW) ? (unsigned)((pix * CIN + lc * 4) * 4) : 0x80000000u;
-      } else {
-        go[u] = (unsigned)(((r - XR) * CIN + lc * 4) * 4);
-      }
-    }
-#define SSG_BN_DMA1(T_, ST_)                                                                                         \
-    { _Pragma("unroll") for (int u = 0; u < TDMA; u++)                                                               \
-        bn_dma16(gblk[u] < XR / 8 ? xrsrc : wrsrc, (unsigned)(uintptr_t)(smem + (ST_) * STG + gblk[u] * 1024), go[u], (T_) * 128); }
-    // fragments: lane (row l32 of a 32-row MFMA tile, channel group h of a 16-channel k-step): hi = logical chunk 4 ks + 2 h, lo = the next one
-    // (the sixth pixel tile of the second wave row does not exist: its fragment reads land in the W1 rows of the stage, its products are
-    // never written -- cheaper than a branch around every MFMA)
-    const int i1s = __builtin_amdgcn_readfirstlane(i1b);
-    int xo[MTW1], xs[MTW1];
-#pragma unroll
-    for (int i = 0; i < MTW1; i++) { const int r = (i1s + i) * 32 + l32; xo[i] = r * 128; xs[i] = (r >> 1) & 7; }
-    const int wr_ = XR + j1b * 32 + l32, wo = wr_ * 128, ws = (wr_ >> 1) & 7;
-    v8h fxh[2][2][MTW1], fxl[2][2][MTW1], fwh[2][2], fwl[2][2];       // [register set][k-step][tile]
-#define SSG_BN_READS1(ST_, S_)                                                                                       \
-    { const unsigned char* sb_ = smem + (ST_) * STG;                                                                 \
-      _Pragma("unroll") for (int ks = 0; ks < 2; ks++) {                                                             \
-        _Pragma("unroll") for (int i = 0; i < MTW1; i++) {                                        \
-          fxh[S_][ks][i] = *reinterpret_cast<const v8h*>(sb_ + xo[i] + (((4 * ks + 2 * h) ^ xs[i]) * 16));           \
-          fxl[S_][ks][i] = *reinterpret_cast<const v8h*>(sb_ + xo[i] + (((4 * ks + 2 * h + 1) ^ xs[i]) * 16)); }     \
-        fwh[S_][ks] = *reinterpret_cast<const v8h*>(sb_ + wo + (((4 * ks + 2 * h) ^ ws) * 16));                       \
-        fwl[S_][ks] = *reinterpret_cast<const v8h*>(sb_ + wo + (((4 * ks + 2 * h + 1) ^ ws) * 16)); } }
-#define SSG_BN_MMAK(S_, KS_)                                                                                         \
-    { _Pragma("unroll") for (int i = 0; i < MTW1; i++) acc1[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fwh[S_][KS_], fxl[S_][KS_][i], acc1[i][0], 0, 0, 0); \
-      _Pragma("unroll") for (int i = 0; i < MTW1; i++) acc1[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fwl[S_][KS_], fxh[S_][KS_][i], acc1[i][0], 0, 0, 0); \
-      _Pragma("unroll") for (int i = 0; i < MTW1; i++) acc1[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fwh[S_][KS_], fxh[S_][KS_][i], acc1[i][0], 0, 0, 0); }
-    // k-tile t (fragments in set S): first k-step, publish tile t + 1 (and: everybody is done reading this stage), refill this stage with
-    // tile t + NS, read tile t + 1's fragments into the other set, second k-step
-#define SSG_BN_STEPD(KT_, ST_, STN_, S_)                                                                             \
-    { SSG_BN_MMAK(S_, 0)                                                                                             \
-      __builtin_amdgcn_sched_barrier(0);                                                                             \
-      asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(TDMA * (NS - 2)) : "memory");                  \
-      { const int tn_ = (KT_) + NS < K::NK1 ? (KT_) + NS : K::NK1 - 1;   /* the tail re-fetches the last tile: uniform vmcnt accounting */ \
-        SSG_BN_DMA1(tn_, ST_) }                                                                                      \
-      SSG_BN_READS1(STN_, 1 - (S_))                                                                                  \
-      __builtin_amdgcn_sched_barrier(0);                                                                             \
-      SSG_BN_MMAK(S_, 1) }
-    SSG_BN_DMA1(0, 0) SSG_BN_DMA1(1, 1) SSG_BN_DMA1(2, 2) SSG_BN_DMA1(3, 3)
-    asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(TDMA * (NS - 1)) : "memory");       // k-tile 0 landed for everybody
-    SSG_BN_READS1(0, 0)
-#pragma unroll 1
-    for (int kt = 0; kt < K::NK1; kt += NS) {
-      SSG_BN_STEPD(kt, 0, 1, 0) SSG_BN_STEPD(kt + 1, 1, 2, 1) SSG_BN_STEPD(kt + 2, 2, 3, 0) SSG_BN_STEPD(kt + 3, 3, 0, 1)
-    }
-    __syncthreads();                       // drains the redundant tail DMAs: the stages are about to become y1 / the W2 stages
-#undef SSG_BN_STEPD
-#undef SSG_BN_MMAK
-#undef SSG_BN_READS1
-#undef SSG_BN_DMA1
-  } else {
   unsigned aoff[AU];
 #pragma unroll
   for (int u = 0; u < AU; u++) {
@@ -319,9 +223,9 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void bottleneck_kernel(Pa
     if ((KT_) + 1 < K::NK1) SSG_BN_STORE1(((S_) + 1) & 1, ((S_) + 1) % K::PD1)                                        \
     __syncthreads();                                                                                                 \
   }
-  static_assert(K::NK1 % K::PD1 == 0 && K::PD1 <= 8, "phase-1 ring of PD1 register sets");
+  static_assert(K::NK1 % K::PD1 == 0 && K::PD1 <= 4, "phase-1 ring of PD1 register sets");
 #define SSG_BN_LOAD1_IF(S_) if constexpr ((S_) < K::PD1) SSG_BN_LOAD1(S_, S_)
-  SSG_BN_LOAD1_IF(0) SSG_BN_LOAD1_IF(1) SSG_BN_LOAD1_IF(2) SSG_BN_LOAD1_IF(3) SSG_BN_LOAD1_IF(4) SSG_BN_LOAD1_IF(5) SSG_BN_LOAD1_IF(6) SSG_BN_LOAD1_IF(7)
+  SSG_BN_LOAD1_IF(0) SSG_BN_LOAD1_IF(1) SSG_BN_LOAD1_IF(2) SSG_BN_LOAD1_IF(3)
 #undef SSG_BN_LOAD1_IF
   SSG_BN_STORE1(0, 0)
   __syncthreads();
@@ -329,29 +233,25 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void bottleneck_kernel(Pa
 #pragma unroll
   for (int kt0 = 0; kt0 < K::NK1; kt0 += K::PD1) {
     SSG_BN_STEP1_IF(kt0, 0) SSG_BN_STEP1_IF(kt0 + 1, 1) SSG_BN_STEP1_IF(kt0 + 2, 2) SSG_BN_STEP1_IF(kt0 + 3, 3)
-    SSG_BN_STEP1_IF(kt0 + 4, 4) SSG_BN_STEP1_IF(kt0 + 5, 5) SSG_BN_STEP1_IF(kt0 + 6, 6) SSG_BN_STEP1_IF(kt0 + 7, 7)
   }
 #undef SSG_BN_STEP1_IF
 #undef SSG_BN_STEP1
-  }
   SSG_BN_STAMP(1)
 #undef SSG_BN_LOAD1
 #undef SSG_BN_STORE1
 #undef SSG_BN_MMA1
 
   // ---- conv2 weights: first k-tiles on their way while y1 is written
-  constexpr int CPR2 = 8 * K::KT2, RP8 = K::NTHR / CPR2, BU = MID / RP8;   // 16-byte pieces per thread and W2 stage (MID rows x KT2 x 128 B)
-  const int ck8 = tid % CPR2, r8 = tid / CPR2;
+  constexpr int RP8 = K::NTHR / 8, BU = MID / RP8;   // 16-byte pieces per thread and W2 stage (MID rows x 128 B)
+  const int ck8 = tid % 8, r8 = tid / 8;
   const float* w2p = p.w2 + (int64_t)r8 * (9 * MID) + ck8 * 4;
   v4f sb2[K::PD2][BU];
 #define SSG_BN_LOAD2(T_, S_)                                                                                         \
-  { _Pragma("unroll") for (int u = 0; u < BU; u++) sb2[S_][u] = *reinterpret_cast<const v4f*>(w2p + (int64_t)(RP8 * u) * (9 * MID) + (T_) * (32 * K::KT2)); }
+  { _Pragma("unroll") for (int u = 0; u < BU; u++) sb2[S_][u] = *reinterpret_cast<const v4f*>(w2p + (int64_t)(RP8 * u) * (9 * MID) + (T_) * 32); }
 #define SSG_BN_STORE2(BUF_, S_)                                                                                      \
   { unsigned char* sb_ = smem + K::W2_OFF + (BUF_) * K::BUF2;                                                        \
     _Pragma("unroll") for (int u = 0; u < BU; u++) *reinterpret_cast<v4f*>(sb_ + (r8 + RP8 * u) * K::P2 + ck8 * 16) = sb2[S_][u]; }
-#define SSG_BN_LOAD2_IF(S_) if constexpr ((S_) < K::PD2) SSG_BN_LOAD2(S_, S_)
-  SSG_BN_LOAD2_IF(0) SSG_BN_LOAD2_IF(1) SSG_BN_LOAD2_IF(2) SSG_BN_LOAD2_IF(3) SSG_BN_LOAD2_IF(4) SSG_BN_LOAD2_IF(5)
-#undef SSG_BN_LOAD2_IF
+  SSG_BN_LOAD2(0, 0) SSG_BN_LOAD2(1, 1) SSG_BN_LOAD2(2, 2) SSG_BN_LOAD2(3, 3) SSG_BN_LOAD2(4, 4) SSG_BN_LOAD2(5, 5)
 
   // ---- y1 -> LDS (h8l8 pixel rows).  Rows outside the image are conv2's zero padding, not relu(bias).
   unsigned ovf = 0u;
@@ -384,32 +284,32 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void bottleneck_kernel(Pa
   SSG_BN_STAMP(2)
 
   // =========================== phase 2: y2 = relu(conv2_3x3(y1)), pixel operand from LDS ===========================
-  // waves: 4 pixel tiles x WC2 channel groups of NT2 channel tiles each
-  constexpr int WC2 = NW / 4, NT2 = MID / 32 / WC2;
-  const int pt2 = wave / WC2, cb2 = (wave % WC2) * NT2;
+  // wave = its own 32-pixel tile x all NT2 channel tiles
+  constexpr int NT2 = MID / 32;
   v16f acc2[NT2];
 #pragma unroll
   for (int j = 0; j < NT2; j++)
 #pragma unroll
     for (int r = 0; r < 16; r++) acc2[j][r] = 0.f;
-  const int m2 = pt2 * 32 + l32, ty2 = m2 / IW, tx2 = m2 - ty2 * IW;       // this lane's output pixel (tile-local)
+  const int m2 = wave * 32 + l32, ty2 = m2 / IW, tx2 = m2 - ty2 * IW;       // this lane's output pixel (tile-local)
   float4 cs2r[NT2][4], b2r[NT2][4];                        // needed right after the loop (NXT: fetched there, its registers do not reach)
   if constexpr (!NXT)
 #pragma unroll
   for (int j = 0; j < NT2; j++)
 #pragma unroll
     for (int q = 0; q < 4; q++) {
-      cs2r[j][q] = *reinterpret_cast<const float4*>(p.cs2 + (cb2 + j) * 32 + 8 * q + 4 * h); b2r[j][q] = *reinterpret_cast<const float4*>(p.b2 + (cb2 + j) * 32 + 8 * q + 4 * h);
+      cs2r[j][q] = *reinterpret_cast<const float4*>(p.cs2 + j * 32 + 8 * q + 4 * h); b2r[j][q] = *reinterpret_cast<const float4*>(p.b2 + j * 32 + 8 * q + 4 * h);
     }
 #define SSG_BN_STEP2(KT_, S_, B_)                                                                                     \
   {                                                                                                                  \
     if ((KT_) + K::PD2 < K::NK2) SSG_BN_LOAD2((KT_) + K::PD2, S_)                                                     \
-    _Pragma("unroll") for (int sub = 0; sub < K::KT2; sub++) {                                                       \
-      const int kt_ = (KT_) * K::KT2 + sub;                                                                          \
-      const int chunk = kt_ / 9, tap = kt_ - chunk * 9, r = tap / 3, s = tap - r * 3;                                \
+    {                                                                                                                \
+      const int chunk = (KT_) / 9, tap = (KT_) - chunk * 9, r = tap / 3, s = tap - r * 3;                            \
       const int xin = tx2 + s - 1;                                                                                   \
-      const int abase = (xin >= 0 && xin < IW) ? ((ty2 + r) * IW + xin) * K::PY : K::ZERO_OFF;                       \
-      const unsigned char* wb = smem + K::W2_OFF + (B_) * K::BUF2 + (cb2 * 32 + l32) * K::P2 + sub * 128 + h * 32;     \
+      const bool inrow = xin >= 0 && xin < IW;                                                                       \
+      const int arow = ((ty2 + r) * IW + xin) * K::PY;     /* (taken unconditionally: a select, not a branch) */     \
+      const int abase = inrow ? arow : K::ZERO_OFF;                                                                  \
+      const unsigned char* wb = smem + K::W2_OFF + (B_) * K::BUF2 + l32 * K::P2 + h * 32;                             \
       v8h xh_[2], xl_[2], wh_[2][NT2], wl_[2][NT2];                                                                  \
       _Pragma("unroll") for (int ks = 0; ks < 2; ks++) {                                                             \
         const unsigned char* q_ = smem + abase + (chunk * 4 + ks * 2 + h) * 32;                                      \
@@ -427,12 +327,12 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void bottleneck_kernel(Pa
     if ((KT_) + 1 < K::NK2) SSG_BN_STORE2((B_) ^ 1, ((S_) + 1) % K::PD2)                                              \
     __syncthreads();                                                                                                 \
   }
-  // six steps per trip: the register set of step i is i % PD2 (PD2 = 6 or 3), its LDS buffer i & 1
-  static_assert(K::NK2 % 6 == 0 && 6 % K::PD2 == 0, "phase-2 ring");
+  // six steps per trip: the register set of step i is i (PD2 = 6), its LDS buffer i & 1
+  static_assert(K::PD2 == 6, "phase-2 ring");
 #pragma unroll
   for (int kt0 = 0; kt0 < K::NK2; kt0 += 6) {
-    SSG_BN_STEP2(kt0, 0 % K::PD2, 0) SSG_BN_STEP2(kt0 + 1, 1 % K::PD2, 1) SSG_BN_STEP2(kt0 + 2, 2 % K::PD2, 0)
-    SSG_BN_STEP2(kt0 + 3, 3 % K::PD2, 1) SSG_BN_STEP2(kt0 + 4, 4 % K::PD2, 0) SSG_BN_STEP2(kt0 + 5, 5 % K::PD2, 1)
+    SSG_BN_STEP2(kt0, 0, 0) SSG_BN_STEP2(kt0 + 1, 1, 1) SSG_BN_STEP2(kt0 + 2, 2, 0)
+    SSG_BN_STEP2(kt0 + 3, 3, 1) SSG_BN_STEP2(kt0 + 4, 4, 0) SSG_BN_STEP2(kt0 + 5, 5, 1)
   }
 #undef SSG_BN_STEP2
   SSG_BN_STAMP(3)
@@ -448,7 +348,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void bottleneck_kernel(Pa
   // acc4[4] += W1n . out (32 pixels x 128 channels per wave).  W3 stages (64 rows x 64 channels) and W1n stages (128 rows x 32
   // channels) take turns in one two-buffer ring behind the wave rows: per pass W3, W1n, W1n; one barrier per stage.
   // k-steps ascend, the three products keep their order: y1n is bit-identical to ssg_conv2d_nhwc_x(out, W1n).
-  static_assert(!DS && NW == 4 && MID == 64 && C == 256 && IW == 32 && NT2 == 2 && WC2 == 1, "the layer1 identity block");
+  static_assert(!DS && MID == 64 && C == 256 && IW == 32 && NT2 == 2, "the layer1 identity block");
   constexpr int MIDN = 128, NCP = 64, NPASS = C / NCP, NSTEP = 3 * NPASS;
   constexpr int P3N = MID * 4 + 16, PN = 144, NXSTG = cmax(NCP * P3N, MIDN * PN);   // stage rows: W3 256 B, W1n 128 B (pitch / 16 odd)
   constexpr int EP = 36, CPR = 8, RPI = 8, ITS = 4;
@@ -516,11 +416,10 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void bottleneck_kernel(Pa
 #pragma unroll
     for (int r = 0; r < 16; r++) acc4[j][r] = 0.f;
   float4 rr[ITS], b3r, cs3r;
-  constexpr int NT_RES = SSG_BN_NT_RES ? 2 : 0, NT_ST = SSG_BN_NT_STORE ? 2 : 0;   // cache-policy operand of the buffer instructions: nt
   // the epilogue operands of channel tile T_ (residual rows, bias, scale): fetched as soon as the tile before has used its own (one
   // register set: two leave no room for acc4), a multiply or more ahead of their use
 #define SSG_BN_NEPIOPS(T_)                                                                                           \
-  { _Pragma("unroll") for (int it = 0; it < ITS; it++) { const v4u t4_ = __builtin_amdgcn_raw_buffer_load_b128(xrsrc, xro, (it * RPI * C + (T_) * 32) * 4, NT_RES);  \
+  { _Pragma("unroll") for (int it = 0; it < ITS; it++) { const v4u t4_ = __builtin_amdgcn_raw_buffer_load_b128(xrsrc, xro, (it * RPI * C + (T_) * 32) * 4, AUX_NT);  \
       rr[it] = make_float4(__uint_as_float(t4_[0]), __uint_as_float(t4_[1]), __uint_as_float(t4_[2]), __uint_as_float(t4_[3])); } \
     b3r = *reinterpret_cast<const float4*>(p.b3 + (T_) * 32 + chunk * 4); cs3r = *reinterpret_cast<const float4*>(p.cs3 + (T_) * 32 + chunk * 4); }
   SSG_BN_NEPIOPS(0)
@@ -570,8 +469,8 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void bottleneck_kernel(Pa
       const unsigned rx = lane_xor1((odd ? hp.x : lp.x)), ry = lane_xor1((odd ? hp.y : lp.y));                       \
       const v4u sv_ = {odd ? rx : hp.x, odd ? ry : hp.y, odd ? lp.x : rx, odd ? lp.y : ry};                          \
       *reinterpret_cast<v4u*>(patch + pr * EP + chunk * 4) = sv_;   /* lanes 2g, 2g + 1: hi x 8 | lo x 8 of channel group g */ \
-      if (p.out) __builtin_amdgcn_raw_buffer_store_b128(sv_, orsrc, tpo, (it * RPI * C + ct_ * 32) * 4, NT_ST);       \
-      if (p.out_s2) __builtin_amdgcn_raw_buffer_store_b128(sv_, srsrc, s2o, (it * (RPI / 2) * C + ct_ * 32) * 4, NT_ST); \
+      if (p.out) __builtin_amdgcn_raw_buffer_store_b128(sv_, orsrc, tpo, (it * RPI * C + ct_ * 32) * 4, AUX_NT);       \
+      if (p.out_s2) __builtin_amdgcn_raw_buffer_store_b128(sv_, srsrc, s2o, (it * (RPI / 2) * C + ct_ * 32) * 4, AUX_NT); \
     }                                                                                                                \
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");                                                           \
     if (ct_ + 1 < C / 32) SSG_BN_NEPIOPS(ct_ + 1)                                                                    \
@@ -644,10 +543,8 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void bottleneck_kernel(Pa
     _Pragma("unroll") for (int u = 0; u < CU3; u++) *reinterpret_cast<v4f*>(sb_ + (r0 + RPP * u) * K::P1 + ck * 16) = sc3[S_][u]; }
   SSG_BN_LOAD3(0, 0)
   SSG_BN_LOAD3(1, 1)
-  // phase-3 waves: 4 pixel tiles x WC3 channel groups of NT3 channel tiles each
-  constexpr int WC3 = NW / 4, NT3 = C / 32 / WC3;
-  const int pt3 = wave / WC3, cb3 = (wave % WC3) * NT3;
-  const int64_t gpix0 = ((int64_t)img * p.H + ty0) * IW + pt3 * 32;        // first output pixel of this wave (pixels are contiguous)
+  constexpr int NT3 = C / 32;                              // phase-3 wave = its own 32-pixel tile x all NT3 channel tiles
+  const int64_t gpix0 = ((int64_t)img * p.H + ty0) * IW + wave * 32;       // first output pixel of this wave (pixels are contiguous)
   // DS: the downsample operand, this lane's pixel, k-tiles MID/16 .. NK3-1 = channels of x: [8 hi][8 lo] of group h per k-tile
   constexpr int NXK = DS ? CIN / 16 : 1;
   v8h xrh[NXK], xrl[NXK];
@@ -656,21 +553,20 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void bottleneck_kernel(Pa
 #pragma unroll
     for (int t = 0; t < NXK; t++) { xrh[t] = *reinterpret_cast<const v8h*>(xq + t * 16); xrl[t] = *reinterpret_cast<const v8h*>(xq + t * 16 + 4); }
   }
-  // y2 rows: phase 2 writes the rows of pixel tile pt2 (its channel group), phase 3 reads those of pt3 (4 waves: the same
-  // wave, 8 waves: a wave pair -- the barrier before the first multiply of phase 3 publishes them either way)
-  unsigned char* myrows = smem + (pt3 * 32) * K::PY;
+  // y2 rows: phase 2 writes the rows of this wave's pixel tile, phase 3 reads the same rows
+  unsigned char* myrows = smem + (wave * 32) * K::PY;
 #pragma unroll
   for (int j = 0; j < NT2; j++)
 #pragma unroll
     for (int q = 0; q < 4; q++) {
-      const int ch = (cb2 + j) * 32 + 8 * q + 4 * h;
+      const int ch = j * 32 + 8 * q + 4 * h;
       const float4 cs = cs2r[j][q], bi = b2r[j][q];
       float4 v = make_float4(acc2[j][4 * q] * cs.x + bi.x, acc2[j][4 * q + 1] * cs.y + bi.y, acc2[j][4 * q + 2] * cs.z + bi.z, acc2[j][4 * q + 3] * cs.w + bi.w);
       v = relu4(v);
       uint2 hi, lo;
       encode4(v, hi, lo);
       ovf |= hi_nonfinite_bits(hi);
-      unsigned char* d = smem + (pt2 * 32 + l32) * K::PY + (ch >> 3) * 32 + h * 8;
+      unsigned char* d = smem + (wave * 32 + l32) * K::PY + (ch >> 3) * 32 + h * 8;
       *reinterpret_cast<uint2*>(d) = hi; *reinterpret_cast<uint2*>(d + 16) = lo;
     }
 
@@ -689,7 +585,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void bottleneck_kernel(Pa
       const unsigned char* q_ = myrows + l32 * K::PY + (((KT_) % (MID / 16)) * 2 + h) * 32;                          \
       xh_ = *reinterpret_cast<const v8h*>(q_); xl_ = *reinterpret_cast<const v8h*>(q_ + 16);                         \
     }                                                                                                                \
-    const unsigned char* wb_ = smem + K::W3_OFF + (BUF_) * K::BUF3 + (cb3 * 32 + l32) * K::P1 + h * 32;              \
+    const unsigned char* wb_ = smem + K::W3_OFF + (BUF_) * K::BUF3 + l32 * K::P1 + h * 32;                           \
     _Pragma("unroll") for (int jj = 0; jj < NT3; jj += 4) {                                                          \
       v8h wh_[4], wl_[4];                                                                                            \
       _Pragma("unroll") for (int j = 0; j < 4; j++) {                                                                \
@@ -705,13 +601,6 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void bottleneck_kernel(Pa
   const float* __restrict__ resp = p.x + gpix0 * C;        // residual (identity blocks only)
   float* __restrict__ outp = p.out + gpix0 * C;
   float4 rr[2][ITS], b3r[2], cs3r[2];
-#ifdef SSG_BN_ABL_NORES                                  // ablation build (tools/micro/bneck_prof.hip): no residual read, wrong results
-#define SSG_BN_RESLOAD(P_) make_float4(0.f, 0.f, 0.f, 0.f)
-#elif SSG_BN_NT_RES                                      // the residual re-read is x's last use: nt cache policy (see SSG_BN_NT_STORE above)
-#define SSG_BN_RESLOAD(P_) ([&]() { const v4f t_ = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(P_)); return make_float4(t_[0], t_[1], t_[2], t_[3]); }())
-#else
-#define SSG_BN_RESLOAD(P_) (*reinterpret_cast<const float4*>(P_))
-#endif
   SSG_BN_STORE3(0, 0)
   SSG_BN_STORE3(1, 1)
   if constexpr (K::NK3 > 2) { SSG_BN_LOAD3(2, 0) SSG_BN_LOAD3(3, 1) }
@@ -728,9 +617,9 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void bottleneck_kernel(Pa
       if constexpr ((R_) + 2 < K::NK3 / 2) { SSG_BN_LOAD3(2 * (R_) + 4, 0) SSG_BN_LOAD3(2 * (R_) + 5, 1) }           \
       else {                                 /* last round ahead: the W3 staging registers are free for the epilogue's first operands */ \
         if constexpr (!DS) {                                                                                         \
-          _Pragma("unroll") for (int it = 0; it < ITS; it++) rr[0][it] = SSG_BN_RESLOAD(resp + (int64_t)(it * RPI + prow) * C + cb3 * 32 + chunk * 4); \
+          _Pragma("unroll") for (int it = 0; it < ITS; it++) rr[0][it] = load_res_nt<C>(resp, it * RPI + prow, chunk * 4); \
         }                                                                                                            \
-        b3r[0] = *reinterpret_cast<const float4*>(p.b3 + cb3 * 32 + chunk * 4); cs3r[0] = *reinterpret_cast<const float4*>(p.cs3 + cb3 * 32 + chunk * 4); \
+        b3r[0] = *reinterpret_cast<const float4*>(p.b3 + chunk * 4); cs3r[0] = *reinterpret_cast<const float4*>(p.cs3 + chunk * 4); \
       }                                                                                                              \
       __syncthreads();                                                                                               \
     }                                                                                                                \
@@ -745,19 +634,14 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void bottleneck_kernel(Pa
   // ---- epilogue: per channel tile a 32-pixel x 32-channel patch through LDS (this wave's own, now dead, y2 rows), then
   // whole 128-byte row segments: bias, residual (x, h8l8), ReLU, re-encode, store.  Same code path as conv.hip.
   static_assert(32 * EP * 4 <= 32 * K::PY, "patch fits in the wave's y2 rows");
-  float* patch;
-  if constexpr (WC3 == 1) patch = reinterpret_cast<float*>(myrows);       // its y2 rows are this wave's alone and dead now
-  else {                                                                  // rows shared by a wave pair: the patches take over the W3 stages
-    __syncthreads();
-    patch = reinterpret_cast<float*>(smem + K::W3_OFF) + wave * (32 * EP);
-  }
+  float* const patch = reinterpret_cast<float*>(myrows);                  // its y2 rows are this wave's alone and dead now
 #pragma unroll
   for (int j = 0; j < NT3; j++) {
-    const int col = (cb3 + j) * 32 + chunk * 4;
+    const int col = j * 32 + chunk * 4;
     if (j + 1 < NT3) {
       if constexpr (!DS) {
 #pragma unroll
-        for (int it = 0; it < ITS; it++) rr[(j + 1) & 1][it] = SSG_BN_RESLOAD(resp + (int64_t)(it * RPI + prow) * C + col + 32);
+        for (int it = 0; it < ITS; it++) rr[(j + 1) & 1][it] = load_res_nt<C>(resp, it * RPI + prow, col + 32);
       }
       b3r[(j + 1) & 1] = *reinterpret_cast<const float4*>(p.b3 + col + 32); cs3r[(j + 1) & 1] = *reinterpret_cast<const float4*>(p.cs3 + col + 32);
     }
@@ -789,11 +673,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void bottleneck_kernel(Pa
       ovf |= hi_nonfinite_bits(hp);
       const unsigned rx = lane_xor1((odd ? hp.x : lp.x)), ry = lane_xor1((odd ? hp.y : lp.y));
       const uint4 stv = make_uint4(odd ? rx : hp.x, odd ? ry : hp.y, odd ? lp.x : rx, odd ? lp.y : ry);
-#if SSG_BN_NT_STORE
-      { const v4u sv_ = {stv.x, stv.y, stv.z, stv.w}; __builtin_nontemporal_store(sv_, reinterpret_cast<v4u*>(outp + (int64_t)pr * C + col)); }
-#else
-      *reinterpret_cast<uint4*>(outp + (int64_t)pr * C + col) = stv;
-#endif
+      store_out_nt(outp + (int64_t)pr * C + col, stv);
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
   }
@@ -803,20 +683,20 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void bottleneck_kernel(Pa
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-// Layer2 in channel halves: the same block, the same 128-pixel tile, as a 4-wave workgroup in <= 80 KB of LDS, so that
-// two workgroups share a CU and one's loads, stores and epilogue arithmetic run under the other's multiplies (what the layer1 instance
-// lives on).  Measured at B = 1000, interleaved with the 8-wave instance: 1.13 -> 1.01 ms per block.
+// Layer2 in channel halves: the same block, the same 128-pixel tile.  With all 128 y1 channels of the halo rows in
+// LDS (85 KB) only one workgroup fits on a CU and its phases run one after the other; in halves the workgroup stays within 80 KB, so that
+// two share a CU as the layer1 instance's do (measured at B = 1000 against such a one-per-CU instance: 1.13 -> 1.01 ms per block).
 //   * y1 in two channel halves: conv2 reduces chunk -> tap -> channel, chunks 0-1 read only y1 channels 0-63, chunks 2-3 only 64-127.
 //     Phase 1 computes all 128 channels in ONE pass over x (every wave owns a channel tile of each half); half 0 goes to LDS (272-byte
 //     pixel rows, 160 halo pixels = 43.5 KB) and feeds 18 (chunk, tap) k-tiles of conv2 while the accumulators of half 1 stay parked in
 //     registers (48 per lane); then half 1 takes over the same LDS rows for the other 18 k-tiles, into the same conv2 accumulators.
-//     (A second phase-1 pass for half 1 instead of the parked registers reads x twice: HBM-bound at 0.98 ms, no faster than 8 waves.)
+//     (A second phase-1 pass for half 1 instead of the parked registers reads x twice: HBM-bound at 0.98 ms, no gain.)
 //   * phase-1 stages: whole 128-byte lines, rows unpadded and XOR-swizzled (two padded stages of 288 rows are 1 KB too large).
 //   * y2 never lives in LDS as rows: each 32 x 32 accumulator tile turns through a wave-private patch (scale, bias, ReLU, encode as
 //     before) and comes back as the MFMA fragments of conv3's pixel operand: 8 k-steps x (hi + lo) = 64 registers.
 //   * conv3 + epilogue in four passes of 128 output channels, each over the whole K = 128 in four 32-channel stages (the W2 stage
 //     shape and buffers); the epilogue is the code path of the kernel above.
-// Every accumulator sees the same products in the same order as in the 8-wave instance: bit-identical.
+// Every accumulator sees the same products in the same order as in the three launches of conv.hip: bit-identical to them.
 template <int C, int MID, int IW, int TH>
 struct CfgH {
   static constexpr int NW = 4, NTHR = NW * 64, HROWS = TH + 2, NPIX1 = HROWS * IW, NPIX = TH * IW;
@@ -1069,11 +949,6 @@ __global__ __launch_bounds__(256, 2) void bottleneck_halves_kernel(Params p) {
   const float* __restrict__ resp = p.x + gpix0 * C;
   float* __restrict__ outp = p.out + gpix0 * C;
   float* const patch = reinterpret_cast<float*>(patchb);
-#if SSG_BN_NT_RES
-#define SSG_BH_RESLOAD(P_) ([&]() { const v4f t_ = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(P_)); return make_float4(t_[0], t_[1], t_[2], t_[3]); }())
-#else
-#define SSG_BH_RESLOAD(P_) (*reinterpret_cast<const float4*>(P_))
-#endif
 #pragma unroll 1
   for (int ps = 0; ps < K::NPASS; ps++) {
     const int cb3 = ps * NT3;
@@ -1089,7 +964,7 @@ __global__ __launch_bounds__(256, 2) void bottleneck_halves_kernel(Params p) {
       const int s_ = ps * K::KT3 + (I_);                                                                             \
       if (s_ + 2 < NS3) SSG_BH_LOAD3(s_ + 2, (I_) & 1)                                                                \
       if constexpr ((I_) == K::KT3 - 1) {    /* the epilogue's first operands (two tiles ahead measures the same: the epilogue is VALU work) */ \
-        _Pragma("unroll") for (int it = 0; it < ITS; it++) rr[0][it] = SSG_BH_RESLOAD(resp + (int64_t)(it * RPI + prow) * C + cb3 * 32 + chunk * 4); \
+        _Pragma("unroll") for (int it = 0; it < ITS; it++) rr[0][it] = load_res_nt<C>(resp, it * RPI + prow, cb3 * 32 + chunk * 4); \
         b3r[0] = *reinterpret_cast<const float4*>(p.b3 + cb3 * 32 + chunk * 4); cs3r[0] = *reinterpret_cast<const float4*>(p.cs3 + cb3 * 32 + chunk * 4); \
       }                                                                                                              \
       const unsigned char* wb_ = smem + K::W2_OFF + ((I_) & 1) * K::BUF2 + l32 * K::P2 + h * 32;                      \
@@ -1116,7 +991,7 @@ __global__ __launch_bounds__(256, 2) void bottleneck_halves_kernel(Params p) {
       const int col = (cb3 + j) * 32 + chunk * 4;
       if (j + 1 < NT3) {
 #pragma unroll
-        for (int it = 0; it < ITS; it++) rr[(j + 1) & 1][it] = SSG_BH_RESLOAD(resp + (int64_t)(it * RPI + prow) * C + col + 32);
+        for (int it = 0; it < ITS; it++) rr[(j + 1) & 1][it] = load_res_nt<C>(resp, it * RPI + prow, col + 32);
         b3r[(j + 1) & 1] = *reinterpret_cast<const float4*>(p.b3 + col + 32); cs3r[(j + 1) & 1] = *reinterpret_cast<const float4*>(p.cs3 + col + 32);
       }
       const float4 bias = b3r[j & 1], cs = cs3r[j & 1];
@@ -1144,16 +1019,11 @@ __global__ __launch_bounds__(256, 2) void bottleneck_halves_kernel(Params p) {
         ovf |= hi_nonfinite_bits(hp);
         const unsigned rx = lane_xor1((odd ? hp.x : lp.x)), ry = lane_xor1((odd ? hp.y : lp.y));
         const uint4 stv = make_uint4(odd ? rx : hp.x, odd ? ry : hp.y, odd ? lp.x : rx, odd ? lp.y : ry);
-#if SSG_BN_NT_STORE
-        { const v4u sv_ = {stv.x, stv.y, stv.z, stv.w}; __builtin_nontemporal_store(sv_, reinterpret_cast<v4u*>(outp + (int64_t)pr * C + col)); }
-#else
-        *reinterpret_cast<uint4*>(outp + (int64_t)pr * C + col) = stv;
-#endif
+        store_out_nt(outp + (int64_t)pr * C + col, stv);
       }
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     }
   }
-#undef SSG_BH_RESLOAD
 #undef SSG_BH_STORE3
 #undef SSG_BH_LOAD3
   if ((ovf & 0x80008000u) && p.overflow) *p.overflow = 1;
@@ -1165,23 +1035,23 @@ __global__ __launch_bounds__(256, 2) void bottleneck_halves_kernel(Params p) {
 
 // 1 when ssg_bottleneck_nhwc_x / ssg_bottleneck_ds_nhwc_x has a kernel for this block shape (CIN == C: identity block):
 //   layer1 of ResNet-50 at 256x128 input: H x 32 x 256, MID 64 (identity blocks and the first block, CIN = 64), 4-row tiles;
-//   layer2 identity blocks: H x 16 x 512, MID 128, 8-row tiles (4 waves in channel halves, or 8 waves: SSG_BN_L2_WAVES)
+//   layer2 identity blocks: H x 16 x 512, MID 128, 8-row tiles (bottleneck_halves_kernel)
 extern "C" int ssg_bottleneck_supported(int H, int W, int CIN, int C, int MID) {
   if (C == 256 && MID == 64 && (CIN == 256 || CIN == 64) && W == 32 && H > 0 && H % 4 == 0) return 1;
   if (C == 512 && MID == 128 && CIN == 512 && W == 16 && H > 0 && H % 8 == 0) return 1;
   return 0;
 }
 
-template <int C, int MID, int IW, int TH, int CIN, int NW, bool NXT = false>
+template <int C, int MID, int IW, int TH, int CIN, bool NXT = false>
 static int launch_bottleneck(const ssg::bneck::Params& p, hipStream_t stream) {
   using namespace ssg::bneck;
-  using K = Cfg<C, MID, IW, TH, CIN, NW>;
+  using K = Cfg<C, MID, IW, TH, CIN>;
   static bool attr_set = false;
   if (!attr_set) {
-    SSG_HIP(hipFuncSetAttribute((const void*)bottleneck_kernel<C, MID, IW, TH, CIN, NW, NXT>, hipFuncAttributeMaxDynamicSharedMemorySize, K::LDS));
+    SSG_HIP(hipFuncSetAttribute((const void*)bottleneck_kernel<C, MID, IW, TH, CIN, NXT>, hipFuncAttributeMaxDynamicSharedMemorySize, K::LDS));
     attr_set = true;
   }
-  hipLaunchKernelGGL((bottleneck_kernel<C, MID, IW, TH, CIN, NW, NXT>), dim3(p.B * (p.H / TH)), dim3(NW * 64), K::LDS, stream, p);
+  hipLaunchKernelGGL((bottleneck_kernel<C, MID, IW, TH, CIN, NXT>), dim3(p.B * (p.H / TH)), dim3(K::NTHR), K::LDS, stream, p);
   SSG_LAUNCH_CHECK("bottleneck_kernel");
   return SSG_OK;
 }
@@ -1199,11 +1069,6 @@ static int launch_bottleneck_halves(const ssg::bneck::Params& p, hipStream_t str
   SSG_LAUNCH_CHECK("bottleneck_halves_kernel");
   return SSG_OK;
 }
-
-// layer2 instance when SSG_BN_L2_WAVES is not set
-#ifndef SSG_BN_L2_WAVES_DEFAULT
-#define SSG_BN_L2_WAVES_DEFAULT 4
-#endif
 
 // Next-conv instance of the layer1 identity block: conv1 of the FOLLOWING block rides in this block's epilogue.
 // whether the embedder routes through it when SSG_BN_L1_NEXT is not set
@@ -1270,17 +1135,10 @@ extern "C" int ssg_bottleneck_nhwc_x(const void* x, const void* w1, const float*
   p.B = B; p.H = H; p.overflow = overflow;
   if (nd.set) {
     p.w1n = nd.w1n; p.b1n = nd.b1n; p.cs1n = nd.cs1n; p.y1n = nd.y1n; p.out_s2 = nd.out_s2;
-    return launch_bottleneck<256, 64, 32, 4, 256, 4, true>(p, stream);
+    return launch_bottleneck<256, 64, 32, 4, 256, true>(p, stream);
   }
-  if (C == 512) {   // layer2: SSG_BN_L2_WAVES = 8 (one 8-wave workgroup per CU) or 4 (channel halves, two workgroups per CU), read per launch
-    const char* e = getenv("SSG_BN_L2_WAVES");
-    const int nw = e && *e ? atoi(e) : SSG_BN_L2_WAVES_DEFAULT;
-    if (nw == 4) return launch_bottleneck_halves<512, 128, 16, 8>(p, stream);
-    if (nw == 8) return launch_bottleneck<512, 128, 16, 8, 512, 8>(p, stream);
-    ssg_set_error("ssg_bottleneck_nhwc_x: SSG_BN_L2_WAVES=%s (4 or 8)", e);
-    return SSG_ERR_INVALID;
-  }
-  return launch_bottleneck<256, 64, 32, 4, 256, 4>(p, stream);
+  if (C == 512) return launch_bottleneck_halves<512, 128, 16, 8>(p, stream);   // layer2
+  return launch_bottleneck<256, 64, 32, 4, 256>(p, stream);
 }
 
 // Bottleneck block with a stride-1 downsample branch (the first block of layer1):
@@ -1298,5 +1156,5 @@ extern "C" int ssg_bottleneck_ds_nhwc_x(const void* x, const void* w1, const flo
   p.x = (const float*)x; p.out = (float*)out;
   p.w1 = (const float*)w1; p.b1 = b1; p.cs1 = cs1; p.w2 = (const float*)w2; p.b2 = b2; p.cs2 = cs2; p.w3 = (const float*)w3cat; p.b3 = b3; p.cs3 = cs3;
   p.B = B; p.H = H; p.overflow = overflow;
-  return launch_bottleneck<256, 64, 32, 4, 64, 4>(p, stream);
+  return launch_bottleneck<256, 64, 32, 4, 64>(p, stream);
 }

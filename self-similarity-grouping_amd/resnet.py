@@ -567,55 +567,40 @@ class ResNet:
             else:
                 check(L.ssg_maxpool3x3s2_nhwc(ptr(y), ptr(p), B, H2, W2, 64, stream()), "ssg_maxpool3x3s2_nhwc")
             y = p
-        # SSG_CONV_PAIR=1 (round 6, experimental, off by default: measured in DESIGN.md section 11): conv3 + residual of an identity block and
-        # conv1 of the next block as one launch (ssg_conv_pair_nhwc_x) where a kernel exists (layer3) and the tiles fill the chip
-        pair = sp and os.environ.get("SSG_CONV_PAIR", "0") == "1"
-        blocks, o1_next, y_is_s2 = net["blocks"], None, False
+        # handed: the (y1n, out_s2) of `_bottleneck`'s next-conv route -- the launch of the block before also ran this block's conv1 and
+        # left out[:, ::2, ::2], all this block reads of its input.  Only an unfused bottleneck with a stride-2 conv2 and a downsample
+        # branch can take it.
+        blocks, handed = net["blocks"], None
         for bi, blk in enumerate(blocks):
             if hooks and bi in hooks:
                 hooks[bi]()
-            if blk.get("kind") == "basic":      # base.py:38-54
-                fused = self._basicblock(L, y, blk, ovf) if sp else None
-                if fused is not None:
+            basic = blk.get("kind") == "basic"      # base.py:38-54
+            if handed is not None and (basic or blk["ds"] is None or blk["c2"].stride != 2 or blk["ds"].stride != 2):
+                raise _lib.SSGError("block %d cannot take the conv1 output and strided input that block %d's launch left for it" % (bi, bi - 1))
+            if sp and handed is None:
+                nxt = blocks[bi + 1] if bi + 1 < len(blocks) else None
+                fused = self._basicblock(L, y, blk, ovf) if basic else self._bottleneck(L, y, blk, ovf, nxt=nxt)
+                if isinstance(fused, tuple):
+                    handed = fused
+                elif fused is not None:
                     y = fused
+                if fused is not None:
                     continue
+            if basic:
                 o = self._conv(L, y, blk["c1"], out_split=sp, ovf=ovf, tiled=tw)
                 r = y if blk["ds"] is None else self._conv(L, y, blk["ds"], relu=False, out_split=sp, ovf=ovf, tiled=tw)
                 y = self._conv(L, o, blk["c2"], res=r, relu=True, out_split=sp, ovf=ovf, tiled=tw)
                 continue
-            if sp:
-                fused = self._bottleneck(L, y, blk, ovf, nxt=blocks[bi + 1] if bi + 1 < len(blocks) else None)
-                if isinstance(fused, tuple):       # the next block's conv1 rode along: y is now out[:, ::2, ::2], all that block reads of it
-                    (o1_next, y), y_is_s2 = fused, True
-                    continue
-                if fused is not None:
-                    y = fused
-                    continue
-            o = o1_next if o1_next is not None else self._conv(L, y, blk["c1"], out_split=sp, ovf=ovf, tiled=tw)
-            o1_next = None
+            if handed is None:
+                o, s2 = self._conv(L, y, blk["c1"], out_split=sp, ovf=ovf, tiled=tw), None
+            else:                                   # y becomes out_s2: only the pixels the downsample branch reads, so its stride is 1
+                (o, y), s2, handed = handed, 1, None
             o = self._conv(L, o, blk["c2"], out_split=sp, ovf=ovf, tiled=tw)
             if blk["ds"] is not None:
-                y = self._conv_dual(L, o, y, blk["c3"], blk["ds"], out_split=sp, ovf=ovf, tiled=tw, stride2=1 if y_is_s2 else None)
-                y_is_s2 = False
-                continue
-            nxt = blocks[bi + 1]["c1"] if bi + 1 < len(blocks) else None
-            Bo, Ho, Wo, _ = o.shape
-            if (pair and nxt is not None and nxt.k == 1 and nxt.stride == 1 and nxt.cin == blk["c3"].cout and Bo * Ho * Wo >= 128 * 256
-                    and L.ssg_conv_pair_supported(blk["c3"].cin, blk["c3"].cout, nxt.cout)):
-                y, o1_next = self._conv_pair(L, o, blk["c3"], y, nxt, ovf)
+                y = self._conv_dual(L, o, y, blk["c3"], blk["ds"], out_split=sp, ovf=ovf, tiled=tw, stride2=s2)
             else:
                 y = self._conv(L, o, blk["c3"], res=y, relu=True, out_split=sp, ovf=ovf, tiled=tw)
         return y, sp
-
-    @staticmethod
-    def _conv_pair(L, o, c3, res, c1n, ovf=None):
-        """(relu(conv3(o) + res), relu(conv1_next(that))) in one launch (ssg_conv_pair_nhwc_x): split-half tensors, 1x1 convolutions"""
-        B, H, W, _ = o.shape
-        out = torch.empty((B, H, W, c3.cout), dtype=torch.float32, device=o.device)
-        y1n = torch.empty((B, H, W, c1n.cout), dtype=torch.float32, device=o.device)
-        check(L.ssg_conv_pair_nhwc_x(ptr(o), ptr(c3.w), ptr(c3.bias), ptr(c3.cscale), ptr(res), ptr(out), ptr(c1n.w), ptr(c1n.bias), ptr(c1n.cscale),
-                                     ptr(y1n), B * H * W, c3.cin, c3.cout, c1n.cout, ptr(ovf), stream()), "ssg_conv_pair_nhwc_x")
-        return out, y1n
 
     # ---- split-half range guard: activations are half pairs, |v| >= 65520 cannot be stored.  Every convolution raises a
     # device flag when it has to encode such a value; the public entry points read it once per call and recompute the batch
@@ -624,10 +609,7 @@ class ResNet:
         """the two HIP streams `embed_with_flip` runs its two forwards on"""
         st = getattr(self, "_streams", None)
         if st is None or st[0].device != self.device:
-            # SSG_FLIP_PRIO=1 (A/B knob, measured in DESIGN.md section 11): the first stream at high priority, so that its launches take the CUs
-            # first and the other forward only fills what they leave -- one kernel's working set in the L2s at a time instead of two
-            prio = -1 if os.environ.get("SSG_FLIP_PRIO", "0") == "1" else 0
-            st = self._streams = (torch.cuda.Stream(self.device, priority=prio), torch.cuda.Stream(self.device))
+            st = self._streams = (torch.cuda.Stream(self.device), torch.cuda.Stream(self.device))
         return st
 
     def _overflow_flag(self):

@@ -1,14 +1,11 @@
-"""GPU suite (-m gpu): the 4-wave "channel halves" instance of the layer2 fused bottleneck block (csrc/bottleneck.hip,
-bottleneck_halves_kernel, picked per launch with SSG_BN_L2_WAVES=4) against the 8-wave instance (SSG_BN_L2_WAVES=8) and against the
-three ssg_conv2d_nhwc_x launches the fused block replaces.  All three run the same products in the same order, so every comparison
+"""GPU suite (-m gpu): the layer2 fused bottleneck block (csrc/bottleneck.hip, bottleneck_halves_kernel: four waves, y1 in channel
+halves) against the three ssg_conv2d_nhwc_x launches it replaces.  Both run the same products in the same order, so every comparison
 is bitwise on the h8l8 output container, and the range flag must agree.
 
 Block: W = 16, C = 512, MID = 128; x is a ReLU output (about half of its values are zero), the weights are random convolutions
 with BatchNorm scales spanning 10^4, folded with per-row power-of-two scales (resnet._fold).
 """
-import contextlib
 import copy
-import os
 
 import pytest
 
@@ -59,29 +56,15 @@ def _x(L, dev, B, H, seed):
     return xs
 
 
-@contextlib.contextmanager
-def _waves(n):
-    old = os.environ.get("SSG_BN_L2_WAVES")
-    os.environ["SSG_BN_L2_WAVES"] = str(n)
-    try:
-        yield
-    finally:
-        if old is None:
-            os.environ.pop("SSG_BN_L2_WAVES", None)
-        else:
-            os.environ["SSG_BN_L2_WAVES"] = old
-
-
-def _fused(L, xs, blk, waves):
-    """-> (out, flag) of ssg_bottleneck_nhwc_x with the 4- or the 8-wave layer2 instance"""
+def _fused(L, xs, blk):
+    """-> (out, flag) of ssg_bottleneck_nhwc_x"""
     from ssg_amd._lib import check, ptr, stream
     c1, c2, c3 = blk
     B, H = xs.shape[0], xs.shape[1]
     out = torch.empty_like(xs)
     flag = torch.zeros(1, dtype=torch.int32, device=xs.device)
-    with _waves(waves):
-        check(L.ssg_bottleneck_nhwc_x(ptr(xs), ptr(c1.w), ptr(c1.bias), ptr(c1.cscale), ptr(c2.w), ptr(c2.bias), ptr(c2.cscale), ptr(c3.w), ptr(c3.bias),
-                                      ptr(c3.cscale), ptr(out), B, H, W, C, MID, ptr(flag), stream()), "bottleneck")
+    check(L.ssg_bottleneck_nhwc_x(ptr(xs), ptr(c1.w), ptr(c1.bias), ptr(c1.cscale), ptr(c2.w), ptr(c2.bias), ptr(c2.cscale), ptr(c3.w), ptr(c3.bias),
+                                  ptr(c3.cscale), ptr(out), B, H, W, C, MID, ptr(flag), stream()), "bottleneck")
     return out, int(flag.item())
 
 
@@ -106,13 +89,11 @@ def test_halves_small_grid(B, H, L, dev, blk):
     tiles, image boundaries inside the grid"""
     assert L.ssg_bottleneck_supported(H, W, C, C, MID) == 1
     xs = _x(L, dev, B, H, 100 * H + B)
-    o4, f4 = _fused(L, xs, blk, 4)
-    o8, f8 = _fused(L, xs, blk, 8)
+    o4, f4 = _fused(L, xs, blk)
     o3, f3 = _three(L, xs, blk)
-    assert (f4, f8, f3) == (0, 0, 0)
-    assert float(o8.abs().max()) > 0
-    assert _same_bits(o4, o8), "4-wave instance != 8-wave instance"
-    assert _same_bits(o4, o3), "4-wave instance != the three launches"
+    assert (f4, f3) == (0, 0)
+    assert float(o3.abs().max()) > 0
+    assert _same_bits(o4, o3), "fused block != the three launches"
 
 
 @pytest.mark.parametrize("half", [0, 1])
@@ -127,46 +108,44 @@ def test_halves_channel_half_wiring(half, L, dev, blk):
     m1.bias = (c1.bias * keep).contiguous()
     masked = (m1, c2, c3)
     xs = _x(L, dev, 2, 24, 7 + half)
-    o4, f4 = _fused(L, xs, masked, 4)
-    o8, f8 = _fused(L, xs, masked, 8)
+    o4, f4 = _fused(L, xs, masked)
     o3, f3 = _three(L, xs, masked)
-    full, _ = _fused(L, xs, blk, 8)
-    assert (f4, f8, f3) == (0, 0, 0)
-    assert not _same_bits(o8, full), "the mask changed nothing"
-    assert _same_bits(o4, o8), "4-wave instance != 8-wave instance (y1 half %d only)" % half
-    assert _same_bits(o4, o3), "4-wave instance != the three launches (y1 half %d only)" % half
+    full, _ = _three(L, xs, blk)
+    assert (f4, f3) == (0, 0)
+    assert not _same_bits(o3, full), "the mask changed nothing"
+    assert _same_bits(o4, o3), "fused block != the three launches (y1 half %d only)" % half
 
 
 def test_halves_co_residency_and_stage_reuse(L, dev, blk):
     """768 workgroups, more than one per CU and two at a time on each: the second phase-1 pass, the W2 / W3 stages and the patches
     reuse LDS that other waves were reading a barrier earlier"""
     xs = _x(L, dev, 192, 32, 19232)
-    a, fa = _fused(L, xs, blk, 4)
-    b, fb = _fused(L, xs, blk, 4)
+    a, fa = _fused(L, xs, blk)
+    b, fb = _fused(L, xs, blk)
     assert (fa, fb) == (0, 0)
     assert _same_bits(a, b), "second launch differs"
     del b
-    o8, f8 = _fused(L, xs, blk, 8)
-    assert f8 == 0
-    assert _same_bits(a, o8), "4-wave instance != 8-wave instance"
+    o3, f3 = _three(L, xs, blk)
+    assert f3 == 0
+    assert _same_bits(a, o3), "fused block != the three launches"
 
 
 def test_halves_overflow_flag(L, dev, blk):
-    """one pixel of x scaled to 6e4 in every channel: its conv1 outputs leave the half range.  Both instances raise the flag, and agree
-    on every pixel outside the 3 x 3 neighbourhood that conv2 spreads the non-finite values over"""
+    """one pixel of x scaled to 6e4 in every channel: its conv1 outputs leave the half range.  The fused block and the three launches both raise the
+    flag, and agree on every pixel outside the 3 x 3 neighbourhood that conv2 spreads the non-finite values over"""
     from ssg_amd._lib import check, ptr, stream
     B, H, py, px = 2, 16, 9, 5
     xs = _x(L, dev, B, H, 4321)
     hot = torch.full((1, C), 6.0e4, device=dev)
     enc = torch.empty_like(hot)
     check(L.ssg_h8l8_encode(ptr(hot), ptr(enc), hot.numel(), 1.0, stream()), "enc")
-    cold4, fc4 = _fused(L, xs, blk, 4)
+    cold4, fc4 = _fused(L, xs, blk)
     assert fc4 == 0
     xs[1, py, px, :] = enc[0]
-    o4, f4 = _fused(L, xs, blk, 4)
-    o8, f8 = _fused(L, xs, blk, 8)
-    assert (f4, f8) == (1, 1)
+    o4, f4 = _fused(L, xs, blk)
+    o3, f3 = _three(L, xs, blk)
+    assert (f4, f3) == (1, 1)
     far = torch.ones(B, H, W, dtype=torch.bool, device=dev)
     far[1, py - 1:py + 2, px - 1:px + 2] = False
-    assert _same_bits(o4[far], o8[far])
+    assert _same_bits(o4[far], o3[far])
     assert _same_bits(o4[far], cold4[far]), "the hot pixel reached pixels beyond its 3 x 3 neighbourhood"

@@ -1,7 +1,7 @@
 // Phase accounting of the fused bottleneck kernel (csrc/bottleneck.hip built with SSG_BN_PROF).
 // build + run on the GPU box:
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -DSSG_BN_PROF -I self-similarity-grouping_amd/csrc tools/micro/bneck_prof.hip -o /tmp/bneck_prof && /tmp/bneck_prof 512
-// -DBN_LAYER2: the 8-wave layer2 instance; -DBN_LAYER2 -DBN_L2H: the 4-wave channel-halves instance (bottleneck_halves_kernel)
+// -DBN_LAYER2: the layer2 block (bottleneck_halves_kernel)
 // -DBN_L1NEXT: the next-conv instance of the layer1 block as the embedder launches it (y1n and out_s2 written, out not)
 #include <cstdio>
 #include <cstdlib>
@@ -18,10 +18,10 @@ static void fill_halves(std::vector<uint16_t>& v, unsigned seed, int emin, int e
 int main(int argc, char** argv) {
   using namespace ssg::bneck;
 #ifdef BN_LAYER2
-  constexpr int KC = 512, KMID = 128, KIW = 16, KTH = 8, KNW = 8;
+  constexpr int KC = 512, KMID = 128, KIW = 16, KTH = 8;
   const int B = argc > 1 ? atoi(argv[1]) : 512, H = 32, W = 16, C = 512, MID = 128;
 #else
-  constexpr int KC = 256, KMID = 64, KIW = 32, KTH = 4, KNW = 4;
+  constexpr int KC = 256, KMID = 64, KIW = 32, KTH = 4;
   const int B = argc > 1 ? atoi(argv[1]) : 512, H = 64, W = 32, C = 256, MID = 64;
 #endif
   const size_t nx = (size_t)B * H * W * C;
@@ -46,26 +46,26 @@ int main(int argc, char** argv) {
   hipMalloc(&wn, hwn.size() * 2); hipMalloc(&y1n, (size_t)B * H * W * 128 * 4); hipMalloc(&os2, nx);
   hipMemcpy(wn, hwn.data(), hwn.size() * 2, hipMemcpyHostToDevice);
   p.out = nullptr; p.w1n = (const float*)wn; p.b1n = bi; p.cs1n = cs; p.y1n = (float*)y1n; p.out_s2 = (float*)os2;
-  using K = Cfg<KC, KMID, KIW, KTH, KC, KNW>;
-  const auto kern = bottleneck_kernel<KC, KMID, KIW, KTH, KC, KNW, true>;
-  constexpr int NTHR = KNW * 64, NPH = 5;
+  using K = Cfg<KC, KMID, KIW, KTH, KC>;
+  const auto kern = bottleneck_kernel<KC, KMID, KIW, KTH, KC, true>;
+  constexpr int NPH = 5;
   const char* names[NPH] = {"phase 1 (conv1 loop)", "y1 write + W2 prologue", "phase 2 (conv2 loop)", "y2 turn + conv3 | epilogue | conv1_next passes", "y1n epilogue"};
-#elif defined(BN_LAYER2) && defined(BN_L2H)
+#elif defined(BN_LAYER2)
   using K = CfgH<KC, KMID, KIW, KTH>;
   const auto kern = bottleneck_halves_kernel<KC, KMID, KIW, KTH>;
-  constexpr int NTHR = K::NTHR, NPH = 5;
+  constexpr int NPH = 5;
   const char* names[NPH] = {"phase 1 (conv1 loop)", "y1 half 0 + conv2 chunks 0-1", "y1 half 1 + conv2 chunks 2-3", "y2 turn + W3 prologue", "conv3 + epilogue, 4 passes"};
 #else
-  using K = Cfg<KC, KMID, KIW, KTH, KC, KNW>;
-  const auto kern = bottleneck_kernel<KC, KMID, KIW, KTH, KC, KNW>;
-  constexpr int NTHR = KNW * 64, NPH = 5;
+  using K = Cfg<KC, KMID, KIW, KTH, KC>;
+  const auto kern = bottleneck_kernel<KC, KMID, KIW, KTH, KC>;
+  constexpr int NPH = 5;
   const char* names[NPH] = {"phase 1 (conv1 loop)", "y1 write + W2 prologue", "phase 2 (conv2 loop)", "y2 write + phase 3 MMA", "epilogue (res + store)"};
 #endif
   hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, K::LDS);
   hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
   for (int rep = 0; rep < 4; rep++) {
     hipEventRecord(e0);
-    hipLaunchKernelGGL(kern, dim3(ntiles), dim3(NTHR), K::LDS, 0, p);
+    hipLaunchKernelGGL(kern, dim3(ntiles), dim3(K::NTHR), K::LDS, 0, p);
     hipEventRecord(e1); hipEventSynchronize(e1);
     float ms; hipEventElapsedTime(&ms, e0, e1);
     printf("B=%d tiles=%d LDS=%d  %.3f ms  (%.2f TB/s x+out)\n", B, ntiles, K::LDS, ms, 2.0 * nx * 4 / ms / 1e9);
