@@ -1002,6 +1002,38 @@ int ssg_hdbscan_core_dist(const void* M, const uint16_t* v, int N, int mode, dou
 int ssg_hdbscan_mst(const void* M, const uint16_t* v, int N, int mode, double lambda_value, const double* core, double alpha, int state,
                     void* ws, size_t ws_bytes, int64_t* current, int64_t* next, double* distance, ssg_stream_t stream);
 
+/* ---- test-time extraction and multi-query pooling (reid/extract_feature.py; csrc/tta.hip) ----------------------------------------------
+ * ssg_tencrop_u8: the script's test-time transform (:47-52) for a batch of equally sized decoded images, bit for bit:
+ *   Resize((RH, RW)) [Pillow bilinear on 8-bit RGB: the arithmetic, tables and scratch of ssg_preprocess_u8] -> TenCrop((CH, CW)) ->
+ *   ToTensor -> Normalize.  src [B,h,w,3] uint8, tmp [B,h,RW,3] uint8 scratch, out [B, ncrops, 3, CH, CW] float32, ncrops 5 or 10.
+ *   crops_host: HOST int32 [5][2], (top, left) of the crops tl, tr, bl, br, centre in the resized image -- torchvision's five_crop; the
+ *   centre is int(round((RH - CH) / 2.0)), int(round((RW - CW) / 2.0)) with Python's round-half-to-even, computed by the caller.
+ *   Crops 5..9 (ncrops = 10) are the same five windows of the horizontally mirrored resized image.  Every resized pixel is filtered
+ *   once and stored into each crop that holds it.  Refused: a non-positive size, CH > RH, CW > RW, ncrops outside {5, 10}, a window
+ *   that leaves the resized image, a NULL pointer.
+ * ssg_crop_mean_f32: out [B, D] = the mean of n feature rows per image = torch's CPU x.view(B, n, -1).mean(1): the ascending
+ *   sequential float32 sum in table order (no fused multiply-add, no float64), divided by (float)n.  src0 [B, nc0, D] and, optionally,
+ *   src1 [B, nc1, D] (nc 5 or 10); table_host: HOST int32 [n][2] = (block 0 | 1, crop), 1 <= n <= 15 (torch sums 16 rows and more
+ *   in cascaded levels).  tail: torch's kernel sums the columns in blocks of SIMD vectors and hands the columns behind the last
+ *   whole block (D % 32 of them in its x86 builds) to a scalar loop with another order: four partial sums p[k] = v[k] + v[4 + k] +
+ *   ... over the whole fours of rows, the remaining rows onto p[0], then ((p[0] + p[1]) + p[2]) + p[3].  The last `tail` columns
+ *   are summed that way; tail = 0 sums every column sequentially.
+ * ssg_group_pool_f32: the multi-query descriptors (:146-153).  x [M, D] float32; order [M]: row indices grouped by key, each group in
+ *   the order its rows were met; offs [G + 1]; qgroup [Q]: the group of every query.  Per row y = (float)((double)x / norm), norm =
+ *   sqrt of the float64 sum of squares (lane l of a wave sums the columns l, l + 64, ... ascending, then a fixed butterfly), 0 counts
+ *   as 1 (sklearn.preprocessing.normalize).  Per group: out_max = the running max of y in group order, NaN once a NaN is met (np.max);
+ *   out_avg = the ascending sequential float32 sum of y in group order / (float)rows (np.mean(axis=0) of a C-contiguous float32
+ *   block).  Each group is computed once, into the row of the first query that names it, and copied to its other queries; no atomics
+ *   on floats, no workspace.  out_max, out_avg [Q, D]; ynorm [M, D] receives y, or NULL.  Any D. */
+int ssg_tencrop_u8(const uint8_t* src, int B, int h, int w, int RH, int RW, int CH, int CW, int ncrops, const int32_t* crops_host,
+                   const int32_t* xmin, const int32_t* xcnt, const int32_t* xk, int xksize, const int32_t* ymin, const int32_t* ycnt,
+                   const int32_t* yk, int yksize, const float* mean3_host, const float* std3_host, uint8_t* tmp, float* out,
+                   ssg_stream_t stream);
+int ssg_crop_mean_f32(const float* src0, int nc0, const float* src1, int nc1, int B, int D, const int32_t* table_host, int n, int tail,
+                      float* out, ssg_stream_t stream);
+int ssg_group_pool_f32(const float* x, int M, int D, const int32_t* order, const int32_t* offs, int G, const int32_t* qgroup, int Q,
+                       float* out_max, float* out_avg, float* ynorm, ssg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

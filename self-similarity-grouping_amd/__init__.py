@@ -98,6 +98,10 @@ def __getattr__(name):   # lazy: torch import only when the compute surface is t
     if name in ("create", "names", "InceptionNet"):      # the model factory with all six names (reid/models/__init__.py)
         from . import inception
         return getattr(inception, name)
+    if name in ("TestDataset", "TestBatchLoader", "FiveCrops", "parse_market_name", "ten_crop_batch", "crop_mean", "extract_feature_matrix",
+                "multi_query_pool", "evaluate"):      # reid/extract_feature.py (its extract_features: ssg_amd.extract_feature.extract_features)
+        from . import extract_feature
+        return getattr(extract_feature, name)
     if name in ("ResNet", "synthetic_state_dict"):
         from . import resnet
         return getattr(resnet, name)

@@ -9,7 +9,8 @@ reference's call surface: `state_dict()` / `load_state_dict()` with the referenc
 pooled feature sets (or their concatenation when for_eval=True), resnet.py:86-134.
 `cluster=True` adds the DEC head (resnet.py:76-77,126-132): the key `assignment.cluster_centers`
 [32, 2048] and a third output x3 = soft assignment of x1 (csrc/dec.hip) wherever the reference
-returns one.
+returns one.  `num_classes=C` (what reid/extract_feature.py builds) adds `classifier_x2.weight` / `.bias`
+and makes x2 the class scores, in eval mode only (resnet.py:118-120 with Dropout as the identity).
 
 The forward runs on hand-written HIP kernels (csrc/conv.hip) through the C ABI: NHWC fp32,
 eval-mode BatchNorm folded into the convolution weights at load time, bias/residual/ReLU
@@ -60,7 +61,7 @@ def _arch(depth):
     return blocks
 
 
-def synthetic_state_dict(seed=1, depth=50, num_features=2048, randomize_bn=True, cluster=False):
+def synthetic_state_dict(seed=1, depth=50, num_features=2048, randomize_bn=True, cluster=False, num_classes=0):
     """Deterministic random weights with the reference's shapes and key names: Kaiming-normal
     fan_out convolutions (reid/models/base.py:113-118), BatchNorm statistics drawn at random so
     that the BN folding is exercised (gamma ~ U(.5,1.5), beta, mean ~ N(0,.1), var ~ U(.5,1.5)).
@@ -108,6 +109,9 @@ def synthetic_state_dict(seed=1, depth=50, num_features=2048, randomize_bn=True,
     if cluster:     # drawn last, so every other tensor is the one cluster=False gets; Xavier uniform like dce.py:29-34
         bound = math.sqrt(6.0 / (_DEC_CLUSTERS + _DEC_DIM))
         sd[_DEC_KEY] = (torch.rand(_DEC_CLUSTERS, _DEC_DIM, generator=g) * 2.0 - 1.0) * bound
+    if num_classes > 0:     # drawn after everything else: every other tensor is the one num_classes=0 gets (resnet.py:72-75)
+        sd["classifier_x2.weight"] = torch.randn(num_classes, num_features, generator=g) * 0.001
+        sd["classifier_x2.bias"] = torch.zeros(num_classes)
     return sd
 
 
@@ -272,9 +276,10 @@ class ResNet:
                  mode='Dissimilarity', cluster=False, seed=1, precision=None):
         if depth not in _LAYERS:
             raise KeyError("Unsupported depth:", depth)
-        if num_classes > 0:
-            raise NotImplementedError("num_classes > 0 (dropout + classifier head, resnet.py:118-120) is a training-only path; "
-                                      "the grouping path uses num_classes=0 (selftraining.py:121-123)")
+        if num_classes > 0 and num_features <= 0:
+            # resnet.py:73: the reference builds nn.Linear(0, num_classes) and dies in its forward, where x2 was never assigned
+            raise ValueError("num_classes = %d needs the embedding it classifies: num_features must be positive (reid/models/resnet.py:73, "
+                             ":118-120)" % num_classes)
         if num_features > 0 and num_features % 64:
             raise ValueError("num_features must be a multiple of 64")
         self.depth, self.num_features, self.dropout, self.num_classes = depth, num_features, dropout, num_classes
@@ -284,7 +289,7 @@ class ResNet:
         if self.precision not in ("split", "f32"):
             raise ValueError("precision must be 'split' or 'f32'")
         self.device = torch.device("cpu")
-        self._sd = synthetic_state_dict(seed, depth, num_features, cluster=bool(cluster))
+        self._sd = synthetic_state_dict(seed, depth, num_features, cluster=bool(cluster), num_classes=max(int(num_classes), 0))
         self._folded = None
         self._twin = None
         # the LDS-DMA convolution launches read their weight stages from the tiled copies (`_attach_tiled`); read at every forward, so both
@@ -666,7 +671,8 @@ class ResNet:
 
     def _x2(self, gap):
         """x2 = relu(feat_bn(feat(gap))) (resnet.py:112-117; unused by the extraction path, which takes
-        model(...)[0]) -- Linear + eval BatchNorm1d folded into one 1x1 GEMM on the same HIP kernel."""
+        model(...)[0]) -- Linear + eval BatchNorm1d folded into one 1x1 GEMM on the same HIP kernel.  With num_classes > 0 the
+        class scores classifier_x2(x2) (ssg_linear_fwd_f32)."""
         if self.num_features <= 0:
             return None
         net = self._prepare()
@@ -684,7 +690,17 @@ class ResNet:
             net["feat"] = f
         B = gap.shape[0]
         out = self._conv(_lib.lib(), gap.reshape(B, 1, 1, self.out_planes).contiguous(), net["feat"], relu=True)
-        return out.reshape(B, self.num_features)
+        out = out.reshape(B, self.num_features)
+        if self.num_classes > 0:
+            # resnet.py:118-120 in eval mode: Dropout is the identity, classifier_x2 is a Linear on nn.Linear's own [N, K] weight
+            if "classifier" not in net:
+                net["classifier"] = tuple(self._sd["classifier_x2." + k].to(self.device, torch.float32).contiguous() for k in ("weight", "bias"))
+            w, b = net["classifier"]
+            logits = torch.empty((B, self.num_classes), dtype=torch.float32, device=out.device)
+            check(_lib.lib().ssg_linear_fwd_f32(ptr(out), ptr(w), ptr(b), ptr(logits), B, self.num_features, self.num_classes, stream()),
+                  "ssg_linear_fwd_f32")
+            return logits
+        return out
 
     def _x3(self, x1):
         """x3 = assignment(x1) (resnet.py:131, dce.py:47-51: always alpha = 1) on the HIP kernel, centres cached on the device"""
