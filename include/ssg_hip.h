@@ -439,7 +439,11 @@ int ssg_half_div_max(const uint16_t* D, const uint32_t* rowmax, int N, uint16_t*
  * (different id or different camera; separate_cams != 0: different camera only, ranking.py:49-51) ordered before
  * the first true match of query q in (distance, gallery index) order, -1 when q has no valid true match;
  * ap[q] = its average precision (step-wise over distinct match distances like sklearn; NaN likewise).
- * *overflow = number of queries with more than 2048 true matches (not evaluated). */
+ * Distances are ordered values: -0.0 == 0.0, and denormals and +-inf are accepted and ordered like any other number.  A NaN is not:
+ * a query with a valid true match and a NaN distance in any valid gallery entry gets first_rank[q] = -2 and ap[q] = NaN (a NaN in
+ * an entry the id / camera filter removes is never read).
+ * *overflow = number of queries that were not evaluated: those with more than 2048 true matches (first_rank -1) plus those marked
+ * -2.  The caller must treat a non-zero word as an error. */
 int ssg_rank_metrics(const float* dist, int m, int n, int64_t ld, const int32_t* qid, const int32_t* qcam, const int32_t* gid,
                      const int32_t* gcam, int separate_cams, int32_t* first_rank, double* ap, int32_t* overflow, ssg_stream_t stream);
 /* the same plus the 'allshots' CMC bins (ranking.py:62-75 with first_match_break=False): nmatch[q] = valid true matches of query q,

@@ -44,7 +44,7 @@ def __getattr__(name):   # lazy: torch import only when the compute surface is t
     if name in ("re_ranking_hausdorff", "re_ranking_hausdorff_device"):
         from . import rerank_hausdorff
         return rerank_hausdorff.re_ranking if name == "re_ranking_hausdorff" else rerank_hausdorff.re_ranking_hausdorff_device
-    if name in ("cmc", "mean_ap", "evaluate_all", "evaluate_same_cams_all", "Evaluator", "single_shot_ranks"):
+    if name in ("cmc", "mean_ap", "evaluate_all", "evaluate_same_cams_all", "Evaluator", "single_shot_ranks", "RankNaNError"):
         from . import ranking
         return getattr(ranking, name)
     if name in ("get_metric", "KISSME", "Euclidean", "validate_cov_matrix"):       # reid/metric_learning/ (the two in-tree learners)

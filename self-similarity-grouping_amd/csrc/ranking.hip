@@ -12,6 +12,12 @@
 // row, binary-searching each valid distance into T and counting per bucket.  AP is then the sum over the
 // distinct match distances of (recall step) x precision, exactly sklearn's step-wise definition (equal
 // scores form one threshold; float64 quotients like sklearn's, summation order differs -> 1e-12 agreement).
+//
+// Distances are ordered values: -0.0 == 0.0, denormals and +-inf take their place in the order like any other number (the
+// reference's CMC accepts them too; tests/rank_ref.py defines the result).  NaN has no place in an order: sklearn's
+// average_precision_score refuses non-finite scores, and here a NaN in a VALID gallery entry of a query that has a valid true match
+// marks the query (first_rank -2, ap NaN) and counts it into *overflow, so the caller raises.  A NaN in an entry the id / camera
+// filter removes is never read.
 #include "ssg_common.h"
 
 namespace ssg {
@@ -27,11 +33,11 @@ __global__ __launch_bounds__(256) void rank_metrics_kernel(const float* __restri
   __shared__ int pj[RK_CAP], sj[RK_CAP];
   __shared__ unsigned hist[RK_CAP + 1];
   __shared__ unsigned hist2[RK_CAP + 1];      // the same by (distance, index) order: bin b = valid entries between match b-1 and match b (incl. match b)
-  __shared__ int npos, before;
+  __shared__ int npos, before, bad;          // bad: a valid entry of this query holds a NaN
   const int q = (int)blockIdx.x, tid = (int)threadIdx.x;
   const float* row = dist + (int64_t)q * ld;
   const int myid = qid[q], mycam = qcam[q];
-  if (tid == 0) { npos = 0; before = 0; }
+  if (tid == 0) { npos = 0; before = 0; bad = 0; }
   for (int t = tid; t <= RK_CAP; t += 256) { hist[t] = 0; hist2[t] = 0; }
   __syncthreads();
   // valid gallery entry: different identity or different camera (ranking.py:47-48,105-106); the 'separate camera set'
@@ -40,7 +46,9 @@ __global__ __launch_bounds__(256) void rank_metrics_kernel(const float* __restri
   for (int j = tid; j < n; j += 256)
     if (gid[j] == myid && is_valid(j)) {
       const int k = atomicAdd(&npos, 1);
-      if (k < RK_CAP) { pd[k] = row[j]; pj[k] = j; }
+      const float x = row[j];
+      if (x != x) bad = 1;
+      if (k < RK_CAP) { pd[k] = x; pj[k] = j; }
     }
   __syncthreads();
   const int P = npos;
@@ -48,6 +56,9 @@ __global__ __launch_bounds__(256) void rank_metrics_kernel(const float* __restri
     if (tid == 0) { first_rank[q] = -1; ap[q] = __longlong_as_double(0x7ff8000000000000LL); if (P > RK_CAP) atomicAdd(overflow, 1); if (nmatch) nmatch[q] = 0; }
     return;
   }
+  // a NaN match has no rank (both comparisons below are false): stop before the sort; a NaN non-match is met in the row pass
+  auto refuse = [&]() { first_rank[q] = -2; ap[q] = __longlong_as_double(0x7ff8000000000000LL); atomicAdd(overflow, 1); if (nmatch) nmatch[q] = 0; };
+  if (bad) { if (tid == 0) refuse(); return; }
   // rank sort of the matches by (distance, index)
   for (int t = tid; t < P; t += 256) {
     const float x = pd[t]; const int jx = pj[t];
@@ -61,6 +72,7 @@ __global__ __launch_bounds__(256) void rank_metrics_kernel(const float* __restri
   for (int j = tid; j < n; j += 256) {
     if (!is_valid(j)) continue;
     const float x = row[j];
+    if (x != x) { bad = 1; continue; }
     int lo = 0, hi = P;                      // lower bound: number of matches with distance < x
     while (lo < hi) { const int mid = (lo + hi) >> 1; if (sd[mid] < x) lo = mid + 1; else hi = mid; }
     atomicAdd(&hist[lo], 1u);
@@ -73,6 +85,7 @@ __global__ __launch_bounds__(256) void rank_metrics_kernel(const float* __restri
   }
   atomicAdd(&before, mine);
   __syncthreads();
+  if (bad) { if (tid == 0) refuse(); return; }
   if (tid == 0) {
     first_rank[q] = before;
     double acc = 0.0, prev_recall = 0.0;
@@ -108,7 +121,8 @@ using namespace ssg;
 
 // first_rank[q] = number of valid gallery entries ordered before query q's first true match in (distance, index)
 // order (-1: no valid true match), ap[q] = average precision (NaN likewise).  dist [m, ld] float32, ids / cams int32.
-// *overflow counts queries with more than 2048 true matches (reported as invalid; the caller raises).
+// *overflow counts the queries that were not evaluated, the caller raises: more than 2048 true matches (first_rank -1), or a NaN
+// distance in a valid gallery entry of a query with a valid true match (first_rank -2).
 static int rank_metrics_impl(const float* dist, int m, int n, int64_t ld, const int32_t* qid, const int32_t* qcam, const int32_t* gid,
                              const int32_t* gcam, int separate_cams, int32_t* first_rank, double* ap, int32_t* overflow, int32_t* nm_before,
                              int32_t* nmatch, int nm_cap, hipStream_t stream) {

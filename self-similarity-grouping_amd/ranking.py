@@ -18,6 +18,12 @@ the call.
 
 Equal distances are ordered by gallery index (numpy's default argsort leaves the tie order unspecified); mAP
 does not depend on it, and CMC only when a true match ties with a non-match.  No CPU fallback.
+
+Distances are ordered values: -0.0 equals 0.0, and denormals, FLT_MAX and +-inf are accepted and take their place in the order like any
+other number (the reference's CMC accepts them too; tests/rank_ref.py defines the result).  NaN is not: a NaN distance in a valid gallery
+entry of a query that has a valid true match raises RankNaNError (sklearn's average_precision_score refuses such scores; the kernel
+would otherwise rank it nowhere), while a NaN in an entry the id / camera filter removes is never read.  Ids and cameras are only ever
+compared for equality: values outside int32 are replaced by their dense ranks, never truncated.
 """
 import contextlib
 import ctypes
@@ -37,32 +43,60 @@ def _dev():
     return torch.device("cuda", torch.cuda.current_device())
 
 
-def _ids(x, n, default, dev):
-    if x is None:
-        x = default(n)
-    return torch.as_tensor(np.asarray(x).astype(np.int64)).to(torch.int32).to(dev).contiguous()
+class RankNaNError(_lib.SSGError):
+    """A NaN distance in a valid gallery entry of a query that has a valid true match: the entry has no place in the ranking, and the
+    reference's mean_ap does not return a number either (sklearn refuses non-finite scores).  Raised instead of a plausible-looking
+    metric; the message names the first such query."""
+
+
+def _int32_labels(query, gallery):
+    """Query and gallery labels (identities, or cameras) -> two int32 numpy arrays that are equal exactly where the given labels are.
+    Equality is all the metrics use, so labels outside int32 are replaced, query and gallery together, by their dense ranks; a cast
+    would make two identities that differ by a multiple of 2^32 one."""
+    query, gallery = np.asarray(query).reshape(-1).astype(np.int64), np.asarray(gallery).reshape(-1).astype(np.int64)
+    both = np.concatenate([query, gallery])
+    if both.size and (both.min() < -2 ** 31 or both.max() >= 2 ** 31):
+        both = np.unique(both, return_inverse=True)[1].reshape(-1)
+    both = both.astype(np.int32)
+    return both[:query.size], both[query.size:]
+
+
+def _prepare(distmat, query_ids, gallery_ids, query_cams, gallery_cams):
+    """what both entry points take -> (float32 CUDA block with unit column stride, its row pitch ld >= n, m, n, qid, qcam, gid, gcam
+    as int32 CUDA tensors); the reference's defaults for lists that are None (ranking.py:26-33)"""
+    dev = _dev()
+    d = torch.as_tensor(distmat).to(dev, torch.float32)
+    if d.dim() != 2:
+        raise ValueError("distmat must be [m, n]")
+    m, n = d.shape
+    if d.stride(1) != 1 or (m > 1 and d.stride(0) < n):          # a transposed or a broadcast block: the kernel reads rows of pitch ld
+        d = d.contiguous()
+    ld = d.stride(0) if m > 1 else n                             # (a single row has no pitch: torch reports any stride for it)
+    qid, gid = _int32_labels(np.arange(m) if query_ids is None else query_ids, np.arange(n) if gallery_ids is None else gallery_ids)
+    qcam, gcam = _int32_labels(np.zeros(m) if query_cams is None else query_cams, np.ones(n) if gallery_cams is None else gallery_cams)
+    if qid.size != m or qcam.size != m or gid.size != n or gcam.size != n:
+        raise ValueError("id / camera lists do not match the distance block")
+    return (d, ld, m, n) + tuple(torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (qid, qcam, gid, gcam))
+
+
+def _raise_unevaluated(first):
+    """the kernel left queries unevaluated (its *overflow word is non-zero): -2 marks a NaN distance, else it is the match cap"""
+    nan = torch.nonzero(first == -2)
+    if nan.numel():
+        raise RankNaNError("ssg_rank_metrics: query %d has a NaN distance in a valid gallery entry" % int(nan[0]))
+    raise _lib.SSGError("ssg_rank_metrics: a query has more than 2048 true matches in the gallery")
 
 
 def per_query(distmat, query_ids=None, gallery_ids=None, query_cams=None, gallery_cams=None, separate_camera_set=False):
     """-> (first_rank int32[m] CUDA, ap float64[m] CUDA); -1 / NaN mark queries without a valid true match."""
     L = _lib.lib()
-    dev = _dev()
-    d = torch.as_tensor(distmat).to(dev, torch.float32)
-    if d.dim() != 2:
-        raise ValueError("distmat must be [m, n]")
-    if d.stride(1) != 1:
-        d = d.contiguous()
-    m, n = d.shape
-    qid = _ids(query_ids, m, np.arange, dev); gid = _ids(gallery_ids, n, np.arange, dev)
-    qcam = _ids(query_cams, m, lambda k: np.zeros(k), dev); gcam = _ids(gallery_cams, n, lambda k: np.ones(k), dev)
-    if qid.numel() != m or qcam.numel() != m or gid.numel() != n or gcam.numel() != n:
-        raise ValueError("id / camera lists do not match the distance block")
-    first = torch.empty(m, dtype=torch.int32, device=dev); ap = torch.empty(m, dtype=torch.float64, device=dev)
-    ovf = torch.zeros(1, dtype=torch.int32, device=dev)
-    check(L.ssg_rank_metrics(ptr(d), m, n, d.stride(0), ptr(qid), ptr(qcam), ptr(gid), ptr(gcam), 1 if separate_camera_set else 0,
+    d, ld, m, n, qid, qcam, gid, gcam = _prepare(distmat, query_ids, gallery_ids, query_cams, gallery_cams)
+    first = torch.empty(m, dtype=torch.int32, device=d.device); ap = torch.empty(m, dtype=torch.float64, device=d.device)
+    ovf = torch.zeros(1, dtype=torch.int32, device=d.device)
+    check(L.ssg_rank_metrics(ptr(d), m, n, ld, ptr(qid), ptr(qcam), ptr(gid), ptr(gcam), 1 if separate_camera_set else 0,
                              ptr(first), ptr(ap), ptr(ovf), stream()), "ssg_rank_metrics")
     if int(ovf.item()):
-        raise _lib.SSGError("ssg_rank_metrics: a query has more than 2048 true matches in the gallery")
+        _raise_unevaluated(first)
     return first, ap
 
 
@@ -70,24 +104,17 @@ def per_query_all(distmat, query_ids=None, gallery_ids=None, query_cams=None, ga
     """-> (nmatch int32[m], nm_before int32[m, cap]) numpy: per query the number of valid true matches and, for its s-th match,
     the number of valid non-matching gallery entries ordered before it (the bins the all-shots CMC credits)."""
     L = _lib.lib()
-    dev = _dev()
-    d = torch.as_tensor(distmat).to(dev, torch.float32)
-    if d.dim() != 2:
-        raise ValueError("distmat must be [m, n]")
-    if d.stride(1) != 1:
-        d = d.contiguous()
-    m, n = d.shape
-    qid = _ids(query_ids, m, np.arange, dev); gid = _ids(gallery_ids, n, np.arange, dev)
-    qcam = _ids(query_cams, m, lambda k: np.zeros(k), dev); gcam = _ids(gallery_cams, n, lambda k: np.ones(k), dev)
+    d, ld, m, n, qid, qcam, gid, gcam = _prepare(distmat, query_ids, gallery_ids, query_cams, gallery_cams)
+    dev = d.device
     cap = int(min(2048, max(1, int(torch.unique(gid, return_counts=True)[1].max().item())))) if n else 1      # no query can have more matches than the largest
     # gallery identity (unique counts, not bincount: raw Market-1501 lists carry the junk pid -1, ids may be large and sparse)
     first = torch.empty(m, dtype=torch.int32, device=dev); ap = torch.empty(m, dtype=torch.float64, device=dev)
     ovf = torch.zeros(1, dtype=torch.int32, device=dev)
     nmb = torch.zeros((m, cap), dtype=torch.int32, device=dev); nm = torch.zeros(m, dtype=torch.int32, device=dev)
-    check(L.ssg_rank_metrics_all(ptr(d), m, n, d.stride(0), ptr(qid), ptr(qcam), ptr(gid), ptr(gcam), 1 if separate_camera_set else 0,
+    check(L.ssg_rank_metrics_all(ptr(d), m, n, ld, ptr(qid), ptr(qcam), ptr(gid), ptr(gcam), 1 if separate_camera_set else 0,
                                  ptr(first), ptr(ap), ptr(ovf), ptr(nmb), ptr(nm), cap, stream()), "ssg_rank_metrics_all")
     if int(ovf.item()):
-        raise _lib.SSGError("ssg_rank_metrics: a query has more than 2048 true matches in the gallery")
+        _raise_unevaluated(first)
     return nm.cpu().numpy(), nmb.cpu().numpy()
 
 
@@ -156,10 +183,8 @@ def _sgs_host_checks(distmat, query_ids, gallery_ids, query_cams, gallery_cams):
         raise ValueError("distmat must be [m, n]")
     m, n = int(shape[0]), int(shape[1])
 
-    def ids(x, k, default):
-        return (default(k) if x is None else np.asarray(x)).astype(np.int64).astype(np.int32).reshape(-1)
-    qid, gid = ids(query_ids, m, np.arange), ids(gallery_ids, n, np.arange)
-    qcam, gcam = ids(query_cams, m, np.zeros), ids(gallery_cams, n, np.ones)
+    qid, gid = _int32_labels(np.arange(m) if query_ids is None else query_ids, np.arange(n) if gallery_ids is None else gallery_ids)
+    qcam, gcam = _int32_labels(np.zeros(m) if query_cams is None else query_cams, np.ones(n) if gallery_cams is None else gallery_cams)
     if qid.size != m or qcam.size != m or gid.size != n or gcam.size != n or m == 0 or n == 0:
         raise ValueError("id / camera lists do not match the distance block")
     if n > SGS_MAX_N:
