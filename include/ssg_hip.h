@@ -1006,6 +1006,37 @@ int ssg_hdbscan_core_dist(const void* M, const uint16_t* v, int N, int mode, dou
 int ssg_hdbscan_mst(const void* M, const uint16_t* v, int N, int mode, double lambda_value, const double* core, double alpha, int state,
                     void* ws, size_t ws_bytes, int64_t* current, int64_t* next, double* distance, ssg_stream_t stream);
 
+/* ---- Agglomerative clustering of a precomputed distance matrix (ssg_amd.agglomerative; csrc/agglomerative.hip) ------------------------
+ * scipy 1.15.3's linkage(y, 'average' | 'complete' | 'single') on the condensed upper triangle -- what sklearn 1.7.2's
+ * AgglomerativeClustering(metric='precomputed', connectivity=None) calls -- with its bits, before the sort of the merges.  The matrix is
+ * a view as above -- mode 0 (M = J' half, v, lambda_value), mode 1 (half) or mode 2 (float64) -- always the whole N x N matrix of one
+ * GPU, widened to float64 element by element; d(i,j) = X[min(i,j), max(i,j)]: the diagonal and the lower triangle take no part.
+ * ssg_agglo_check: one pass over the WHOLE matrix.  counts[0] = the entries that are NaN, counts[1] = the entries that are +inf or -inf.
+ *   counts: two int64 words, zeroed by the call.
+ * ssg_agglo_expand: W[i * ld + j] = W[j * ld + i] = d(i,j) for i != j, W[i * ld + i] = 0: the float64 working square, the only N x N
+ *   write (8 N ld bytes).  ld >= N doubles between two rows, ld % 4 == 0, W 32-byte aligned; the columns N .. ld - 1 are left alone.
+ * ssg_agglo_nn_chain: the merge loop in ONE workgroup; it rewrites W.  It returns at once, writing nothing, when counts[0] or counts[1]
+ *   (the words ssg_agglo_check wrote, read on the device) is not zero.
+ *   method 0 (average), 1 (complete): scipy's nn_chain.  A scan from x = chain[-1] finds the live slot i != x of smallest W[x,i], the
+ *   lowest index on ties, except that chain[-2] keeps every tie with the minimum; it ends the walk when it finds chain[-2], else it
+ *   pushes.  A merge pops two slots, a < b: x[k] = a, y[k] = b, distance[k] = W[a,b], size[k] = size[a] + size[b]; slot a dies, and for
+ *   every live i != b  W[i,b] = W[b,i] = max(W[i,a], W[i,b])  or  (na * W[i,a] + nb * W[i,b]) / (na + nb), two products, one sum and
+ *   one quotient rounded once each, never fused.  At most 3 (N - 1) scans are made; the kernel counts them and stops there.
+ *   method 2 (single): scipy's mst_single_linkage, Prim from node 0: m[j] = min(m[j], W[c,j]) over the unmerged j, next = the unmerged
+ *   node of smallest m, the lowest index on ties; x[k] = c, y[k] = next, distance[k] = m[next]; size is not written (may be NULL).
+ *   x, y, size [N - 1] int64, distance [N - 1] float64, in merge order.  flag: two int64 words, zeroed by the call: flag[0] = 0, or 1
+ *   when the scan bound was reached, or 2 when a scan found no live slot (neither can happen on a finite matrix); flag[1] = the scans
+ *   (single: the steps) made.  state: where the loop keeps size[] and chain[] (single: m[]) -- 1 = LDS (N <= ssg_agglo_lds_max_n()),
+ *   2 = global memory (ws: 8 * ((N + 3) & ~3) bytes, 16-byte aligned), 0 = LDS when it fits, else global; every placement gives the
+ *   same bits.  No synchronisation between workgroups, no spin loop, no atomic.
+ * Refused with SSG_ERR_INVALID before any device call: a null or misaligned pointer, N < 2, a mode outside 0..2, mode 0 without v, an
+ *   ld below N or not a multiple of 4, a method or state outside 0..2, state 1 with N too large, the global state without its workspace. */
+int ssg_agglo_lds_max_n(void);
+int ssg_agglo_check(const void* M, const uint16_t* v, int N, int mode, double lambda_value, int64_t* counts, ssg_stream_t stream);
+int ssg_agglo_expand(const void* M, const uint16_t* v, int N, int mode, double lambda_value, double* W, int64_t ld, ssg_stream_t stream);
+int ssg_agglo_nn_chain(double* W, int N, int64_t ld, int method, int state, const int64_t* counts, void* ws, size_t ws_bytes, int64_t* x, int64_t* y,
+                       double* distance, int64_t* size, int64_t* flag, ssg_stream_t stream);
+
 /* ---- test-time extraction and multi-query pooling (reid/extract_feature.py; csrc/tta.hip) ----------------------------------------------
  * ssg_tencrop_u8: the script's test-time transform (:47-52) for a batch of equally sized decoded images, bit for bit:
  *   Resize((RH, RW)) [Pillow bilinear on 8-bit RGB: the arithmetic, tables and scratch of ssg_preprocess_u8] -> TenCrop((CH, CW)) ->

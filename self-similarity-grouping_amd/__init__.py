@@ -30,8 +30,11 @@ def __getattr__(name):   # lazy: torch import only when the compute surface is t
     if name == "HDBSCAN":
         from . import hdbscan
         return hdbscan.HDBSCAN
-    if name in ("compute_dist", "generate_selflabel", "generate_selflabel_affinity", "generate_selflabel_optics", "generate_selflabel_hdbscan", "select_labeled",
-                "generate_dataset"):
+    if name == "AgglomerativeClustering":
+        from . import agglomerative
+        return agglomerative.AgglomerativeClustering
+    if name in ("compute_dist", "generate_selflabel", "generate_selflabel_affinity", "generate_selflabel_optics", "generate_selflabel_hdbscan",
+                "generate_selflabel_agglomerative", "select_labeled", "generate_dataset"):
         from . import selftraining
         return getattr(selftraining, name)
     if name in ("extract_features", "extract_embeddings", "extract_cnn_feature", "fliplr", "pairwise_distance", "pairwise_distance_device",

@@ -898,3 +898,6 @@ class AffinityPropagation:
 from .optics import OPTICS, cluster_optics_dbscan, cluster_optics_xi, compute_optics_graph  # noqa: E402,F401
 # HDBSCAN (ssg_amd/hdbscan.py: the check, the core distances and the spanning tree on the device, the tree stages on the host) likewise
 from .hdbscan import HDBSCAN  # noqa: E402,F401
+# AgglomerativeClustering (ssg_amd/agglomerative.py: the check, the working square and the merge loop on the device, the sort, the labelling
+# of the tree and the cut on the host) likewise
+from .agglomerative import AgglomerativeClustering  # noqa: E402,F401

@@ -193,6 +193,37 @@ def generate_selflabel_hdbscan(e_dist, r_dist, n_iter, args, cluster_list=[]):  
     return labels_list, cluster_list
 
 
+def generate_selflabel_agglomerative(e_dist, r_dist, n_iter, args, cluster_list=[]):   # noqa: B006 (mutable default kept: reference :280)
+    """selftraining.py:280-313 with bottom-up clustering in the place of DBSCAN: average or complete linkage cut at a distance gives
+    compact clusters whose mean distance or diameter the cut bounds (the grouping of BUC and its successors).  The estimator is created
+    at iteration 0 and cached in `cluster_list`; `args` needs `.no_rerank` and may carry `.agglo_linkage` ('average'), `.agglo_threshold`
+    (None), `.agglo_n_clusters` (None) and `.agglo_min_cluster_size` (4, the reference's DBSCAN min_samples).  With neither a threshold
+    nor a number of clusters the cut is the reference's rho rule (`cluster.eps_rule(dist, args.rho)`) at iteration 0, printed with the
+    reference's line and frozen on the cached estimator like selftraining.py:283-298.  Clusters of fewer than `agglo_min_cluster_size`
+    samples become -1 (generate_dataset drops them as it drops DBSCAN noise), the others are renumbered 0 .. k - 1 in order of first
+    appearance.  One GPU only."""
+    from .agglomerative import AgglomerativeClustering, _drop_small
+    labels_list = []
+    for s in range(len(r_dist)):
+        tmp_dist = e_dist[s] if args.no_rerank else r_dist[s]
+        if n_iter == 0:
+            threshold, n_clusters = getattr(args, "agglo_threshold", None), getattr(args, "agglo_n_clusters", None)
+            if threshold is None and n_clusters is None:
+                threshold = float(eps_rule(tmp_dist, args.rho)[0])
+                print('eps in cluster: {:.3f}'.format(threshold))
+            cluster = AgglomerativeClustering(n_clusters=n_clusters, metric='precomputed', linkage=getattr(args, "agglo_linkage", "average"),
+                                              distance_threshold=threshold)
+            cluster_list.append(cluster)
+        else:
+            cluster = cluster_list[s]
+        print('Clustering and labeling...')
+        labels = _drop_small(cluster.fit_predict(tmp_dist), int(getattr(args, "agglo_min_cluster_size", 4)))
+        num_ids = len(set(labels[labels >= 0].tolist()))
+        print('Iteration {} have {} training ids'.format(n_iter + 1, num_ids))
+        labels_list.append(labels)
+    return labels_list, cluster_list
+
+
 def select_labeled(labels_list):
     """selftraining.py:315-324 join: keep sample i iff no split labelled it -1.
     Returns (kept indices, [per-split label lists])."""
