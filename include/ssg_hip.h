@@ -1037,6 +1037,48 @@ int ssg_agglo_expand(const void* M, const uint16_t* v, int N, int mode, double l
 int ssg_agglo_nn_chain(double* W, int N, int64_t ld, int method, int state, const int64_t* counts, void* ws, size_t ws_bytes, int64_t* x, int64_t* y,
                        double* distance, int64_t* size, int64_t* flag, ssg_stream_t stream);
 
+/* ---- Silhouette coefficient of labelings of a precomputed distance matrix (ssg_amd.silhouette; csrc/silhouette.hip) ---------------------
+ * The N x N part of sklearn 1.7.2's silhouette_samples(X, labels, metric='precomputed') -- _silhouette_reduce -- with its bits, for K
+ * labelings in ONE pass over the matrix.  The matrix is a view as above -- mode 0 (M = J' half, v, lambda_value), mode 1 (half) or mode 2
+ * (float64) -- always the whole N x N matrix of one GPU, widened to float64 element by element and never modified.
+ * The selection: sel [m] int32 on the device, the selected samples in the order in which their columns are added (a sub-matrix
+ *   X[sel][:, sel]; sklearn's sample_size hands over a permuted order); NULL = the identity, m = N.  sel_host: a HOST copy of sel, or
+ *   NULL; when given, every entry is range-checked before the launch.  On the device an entry outside [0, N) is not dereferenced (its
+ *   value enters as NaN).
+ * ssg_silhouette_sums: for labeling k and position a (row sel[a]):
+ *     intra_sum[k * m + a] = s[a, own],   inter_min[k * m + a] = min over c != own of s[a, c] / double(freq[c]),
+ *   s[a, c] = the float64 sum of X[sel[a], sel[b]] over the members b of cluster c: it starts at +0.0, walks the members in ASCENDING
+ *   POSITION and rounds once per add -- np.bincount(labels, weights=row) -- and the quotient is the IEEE division.  Per labeling:
+ *   labels [K, m] int32, the encoded label 0 .. C_k - 1 of every position, or a negative value: that position takes no part in
+ *   labeling k -- it is in no member list and its two outputs are left as the caller set them.  This is how per-labeling noise sets
+ *   are carried (the choice between a per-labeling sel and grouping equal noise sets): sel stays shared, every labeling drops its own
+ *   positions and selects m_k = start[k, C_k] <= m of them, so K labelings with K different noise sets still cost one pass.
+ *   members [K, m] int32: the positions grouped by cluster, ascending inside each cluster (a stable counting sort, built by the caller);
+ *   start [K, Cmax + 1] int32: cluster c of labeling k owns members[k, start[k,c] .. start[k,c+1]); freq[c] is that length.  ncl [K]
+ *   int32: C_k <= Cmax.  Every index read from these arrays is clamped before it is used.  diag: 0 = the entry of a position in its own
+ *   row enters as stored, 1 = it enters as +0.0 (the matrix after np.fill_diagonal(X, 0), without writing it).
+ *   negatives: one int64 word, zeroed by the call: the number of entries of X[sel][:, sel] (after diag) that are below zero, which
+ *   sklearn's pairwise_distances refuses; -0.0 is not counted.  An integer atomic per wave, the only atomic of the kernel.
+ *   A workgroup owns one selected row at a time: it decodes the m selected entries once into a float64 stage, then for each labeling
+ *   thread t of T sums the clusters t, t + T, ... one member after the other, divides, and the workgroup folds the minimum (the caller
+ *   refuses NaN and infinity beforehand -- ssg_agglo_check -- so the fold order does not matter).  No float atomic, no synchronisation
+ *   between workgroups, no spin loop; every loop is bounded by m or by the number of clusters.  T = 256 threads, or 512 or 1024 when
+ *   a CU's LDS holds fewer than four or two stages.  state: where the stage lives -- 1 = LDS
+ *   (m <= ssg_silhouette_lds_max_m()), 2 = global memory (ws: one slice of 8 * ((m + 1) & ~1) bytes per workgroup, 16-byte aligned; as
+ *   many workgroups run as ws_bytes holds slices, at most 1024), 0 = LDS when it fits, else global; every placement gives the same bits.
+ * ssg_silhouette_diag: count[0] = the number of selected samples i with |X[i,i]| > atol, one read per sample; count: one int64 word,
+ *   zeroed by the call.
+ * The NaN / infinity counts over the whole matrix are ssg_agglo_check's.
+ * Refused with SSG_ERR_INVALID before any device call: a null or misaligned pointer, a mode outside 0..2, mode 0 without v, m < 3
+ *   (diag: m < 1), m > N, m != N without sel, a sel_host entry outside [0, N), K < 1, Cmax outside [1, m], diag outside 0..1, a negative
+ *   or NaN atol, a state outside 0..2, state 1 with m too large, the global stage without its workspace. */
+int ssg_silhouette_lds_max_m(void);
+int ssg_silhouette_diag(const void* M, const uint16_t* v, int N, int mode, double lambda_value, const int32_t* sel, const int32_t* sel_host, int m,
+                        double atol, int64_t* count, ssg_stream_t stream);
+int ssg_silhouette_sums(const void* M, const uint16_t* v, int N, int mode, double lambda_value, const int32_t* sel, const int32_t* sel_host, int m,
+                        int K, int Cmax, const int32_t* labels, const int32_t* members, const int32_t* start, const int32_t* ncl, int diag, int state,
+                        void* ws, size_t ws_bytes, double* intra_sum, double* inter_min, int64_t* negatives, ssg_stream_t stream);
+
 /* ---- test-time extraction and multi-query pooling (reid/extract_feature.py; csrc/tta.hip) ----------------------------------------------
  * ssg_tencrop_u8: the script's test-time transform (:47-52) for a batch of equally sized decoded images, bit for bit:
  *   Resize((RH, RW)) [Pillow bilinear on 8-bit RGB: the arithmetic, tables and scratch of ssg_preprocess_u8] -> TenCrop((CH, CW)) ->

@@ -33,8 +33,11 @@ def __getattr__(name):   # lazy: torch import only when the compute surface is t
     if name == "AgglomerativeClustering":
         from . import agglomerative
         return agglomerative.AgglomerativeClustering
+    if name in ("silhouette_samples", "silhouette_score", "silhouette_many"):
+        from . import silhouette
+        return getattr(silhouette, name)
     if name in ("compute_dist", "generate_selflabel", "generate_selflabel_affinity", "generate_selflabel_optics", "generate_selflabel_hdbscan",
-                "generate_selflabel_agglomerative", "select_labeled", "generate_dataset"):
+                "generate_selflabel_agglomerative", "generate_selflabel_sweep", "select_labeled", "generate_dataset"):
         from . import selftraining
         return getattr(selftraining, name)
     if name in ("extract_features", "extract_embeddings", "extract_cnn_feature", "fliplr", "pairwise_distance", "pairwise_distance_device",

@@ -901,3 +901,5 @@ from .hdbscan import HDBSCAN  # noqa: E402,F401
 # AgglomerativeClustering (ssg_amd/agglomerative.py: the check, the working square and the merge loop on the device, the sort, the labelling
 # of the tree and the cut on the host) likewise
 from .agglomerative import AgglomerativeClustering  # noqa: E402,F401
+# the silhouette coefficient (ssg_amd/silhouette.py: the per-row cluster sums on the device, sklearn's finishing lines on the host) likewise
+from .silhouette import silhouette_many, silhouette_samples, silhouette_score  # noqa: E402,F401

@@ -224,6 +224,44 @@ def generate_selflabel_agglomerative(e_dist, r_dist, n_iter, args, cluster_list=
     return labels_list, cluster_list
 
 
+def generate_selflabel_sweep(e_dist, r_dist, n_iter, args, cluster_list=[]):   # noqa: B006 (mutable default kept: reference :280)
+    """selftraining.py:280-313 with a silhouette-driven choice of eps in the place of the single frozen cut.  At iteration 0 the
+    reference's rho rule gives eps0 (`cluster.eps_rule(dist, args.rho)`, printed with the reference's line) and an
+    `OPTICS(metric='precomputed', cluster_method='dbscan', eps=eps0)` is cached in `cluster_list`.  Every iteration fits it once, takes
+    the DBSCAN-like labels of the ordering at eps0 * f for every f of `.sweep_factors` ((0.6, 0.8, 1.0, 1.25, 1.5)) in O(N) each, scores
+    all cuts in ONE pass over the matrix (`silhouette_many(dist, cuts, diagonal='zero', ignore_noise=True)`) and keeps the cut
+    `silhouette.select_cut` chooses: the largest sum of the silhouettes of the clustered samples / N, noise counting as 0, the first
+    maximum in list order, the factor 1.0 when no cut can be scored.  `args` needs `.no_rerank` and `.rho` and may carry
+    `.sweep_factors` and `.sweep_min_samples` (4).  The estimator keeps `labels_` (the chosen cut), `sweep_factor_`, `sweep_eps_` and
+    `sweep_scores_`.  The score is a heuristic whose effect on re-ID accuracy nobody has measured; the function is opt-in.  One GPU only."""
+    from .optics import OPTICS, cluster_optics_dbscan
+    from .silhouette import select_cut, silhouette_many
+    labels_list = []
+    for s in range(len(r_dist)):
+        tmp_dist = e_dist[s] if args.no_rerank else r_dist[s]
+        if n_iter == 0:
+            eps0 = float(eps_rule(tmp_dist, args.rho)[0])
+            print('eps in cluster: {:.3f}'.format(eps0))
+            cluster = OPTICS(metric='precomputed', cluster_method='dbscan', eps=eps0, min_samples=getattr(args, "sweep_min_samples", 4))
+            cluster_list.append(cluster)
+        else:
+            cluster = cluster_list[s]
+        print('Clustering and labeling...')
+        cluster.fit(tmp_dist)
+        factors = [float(f) for f in getattr(args, "sweep_factors", (0.6, 0.8, 1.0, 1.25, 1.5))]
+        cuts = [cluster_optics_dbscan(reachability=cluster.reachability_, core_distances=cluster.core_distances_, ordering=cluster.ordering_,
+                                      eps=cluster.eps * f) for f in factors]
+        best, scores = select_cut(factors, cuts, lambda valid: silhouette_many(tmp_dist, valid, diagonal='zero', ignore_noise=True))
+        labels = cuts[best]
+        cluster.labels_, cluster.sweep_factor_, cluster.sweep_eps_, cluster.sweep_scores_ = labels, factors[best], cluster.eps * factors[best], scores
+        print('sweep factors {} scores {} -> factor {} (eps {:.3f})'.format(
+            factors, ['skipped' if x is None else '{:.4f}'.format(x) for x in scores], factors[best], cluster.sweep_eps_))
+        num_ids = len(set(labels[labels >= 0].tolist()))
+        print('Iteration {} have {} training ids'.format(n_iter + 1, num_ids))
+        labels_list.append(labels)
+    return labels_list, cluster_list
+
+
 def select_labeled(labels_list):
     """selftraining.py:315-324 join: keep sample i iff no split labelled it -1.
     Returns (kept indices, [per-split label lists])."""
