@@ -27,6 +27,19 @@ CASES = {
 # one multi-slice case per weight-gradient kernel (H, W, Cin, Cout, k, seed); B comes from ssg_conv_wgrad_strided_num_slices.
 # 8 x 8 input -> 16 output pixels per image, so that a ragged third slice appears at a B <= 64 with the 256-pixel slice floor
 MULTI = {"multi_1x1": (8, 8, 64, 64, 1, 313), "multi_3x3": (8, 8, 64, 128, 3, 314), "multi_stem": (8, 8, 3, 64, 7, 315)}
+# one case per distinct stride-2 (Cin, Cout, k) of torchvision's ResNet-50 at a 256 x 128 input: the real channel pair on the real
+# input row width, even sides (the real parity), B and H chosen so that the output pixels M = B OH OW give 512 < M < 768 with M no
+# multiple of 64: three weight-gradient slices of which the last is shorter, a ragged last 128-row tile in the forward, and in each
+# parity class of dX (M pixels each) a ragged last 64-pixel tile (test_gpu_conv_strided.py::test_real_cases_have_three_slices_and_ragged_tiles)
+REAL = {
+    "real_3x3_128_128": (5, 14, 32, 128, 128, 3, 320),       # M = 5 * 7 * 16 = 560
+    "real_3x3_256_256": (11, 14, 16, 256, 256, 3, 321),      # M = 11 * 7 * 8 = 616
+    "real_3x3_512_512": (19, 16, 8, 512, 512, 3, 322),       # M = 19 * 8 * 4 = 608
+    "real_1x1_256_512": (5, 14, 32, 256, 512, 1, 323),
+    "real_1x1_512_1024": (11, 14, 16, 512, 1024, 1, 324),
+    "real_1x1_1024_2048": (19, 16, 8, 1024, 2048, 1, 325),
+}
+DOWNSAMPLE = ("real_1x1_256_512", "real_1x1_512_1024", "real_1x1_1024_2048")
 
 
 def out_hw(H, W, k):
@@ -61,6 +74,12 @@ def reference(B, H, W, cin, cout, k, seed):
     OH, OW = out_hw(H, W, k)
     L = dict(y=k * k * cin, dx=k * k * cout, dw=B * OH * OW)
     return d, ref, A, L
+
+
+def pack_dgrad_s2(w):
+    """[Cout,Cin,KH,KW] -> the strided data gradient's packing [KH*KW][Cout][Cin] (tap r*KW + s outermost, Cin contiguous)"""
+    cout, cin, kh, kw = w.shape
+    return w.permute(2, 3, 0, 1).reshape(kh * kw, cout, cin).contiguous()
 
 
 def multi_slice_batch(L, H, W, cin, cout, k):

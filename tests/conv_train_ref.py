@@ -19,6 +19,29 @@ CASES = {
 MULTI = {"multi_1x1": (8, 4, 64, 64, 1, 206), "multi_3x3": (8, 4, 64, 64, 3, 207)}   # (H, W, Cin, Cout, k, seed)
 
 
+def _real():
+    """one case per distinct stride-1 (Cin, Cout, k) of torchvision's ResNet-50 at a 256 x 128 input: the real channel pair on the real
+    row width W, with B and H chosen so that 512 < M = B H W < 768 and M is no multiple of 128 or of 3 -- three weight-gradient slices
+    that cannot be equal, so the last is shorter, and a ragged last 128-row tile in the forward and the data gradient (asserted from the library's slice
+    count in test_gpu_conv_train.py::test_real_cases_have_three_slices_and_ragged_tiles)"""
+    rows = {32: (2, 11), 16: (5, 7), 8: (7, 11), 4: (19, 8)}                    # W -> (B, H): M = 704, 560, 616, 608, no multiple of 3
+    layers = [(1, 32, [(64, 64), (64, 256), (256, 64), (256, 128)]), (1, 16, [(128, 512), (512, 128), (512, 256)]),
+              (1, 8, [(256, 1024), (1024, 256), (1024, 512)]), (1, 4, [(512, 2048), (2048, 512)]),
+              (3, 32, [(64, 64)]), (3, 16, [(128, 128)]), (3, 8, [(256, 256)]), (3, 4, [(512, 512)])]
+    out, seed = {}, 220
+    for k, W, pairs in layers:
+        for cin, cout in pairs:
+            out["real_%dx%d_%d_%d" % (k, k, cin, cout)] = rows[W] + (W, cin, cout, k, seed)
+            seed += 1
+    return out
+
+
+REAL = _real()
+
+# layer1's two 1x1 shapes at the trainer's own batch: name -> (B, H, W, Cin, Cout, seed), M = 131072
+TRAINER = {"trainer_256_64": (64, 64, 32, 256, 64, 251), "trainer_64_256": (64, 64, 32, 64, 256, 252)}
+
+
 def make_case(B, H, W, cin, cout, k, seed):
     g = torch.Generator().manual_seed(seed)
     x = torch.randn(B, cin, H, W, generator=g, dtype=torch.float32)
@@ -73,6 +96,34 @@ def multi_slice_batch(L, H, W, cin, cout, k):
         if L.ssg_conv_wgrad_num_slices(B * H * W, cout, k, k, cin) >= 3:
             return B
     return None
+
+
+@lru_cache(maxsize=1)
+def gemm_reference(name):
+    """(case, ref64 {y, dx, dw}, A {y, dx, dw}) of a TRAINER case.  A 1x1 convolution is a GEMM over the M = B H W pixels, so the
+    reference is three float64 matmuls (three more on absolute values for A) on the NHWC pixel matrices: x [M, Cin], w [Cout, Cin],
+    gy [M, Cout] -> y [M, Cout] = x w^T, dx [M, Cin] = gy w, dw [Cout, Cin] = gy^T x.  Only the last one is kept (hundreds of MB).
+
+    The data are what these layers see: x = max(N(0, 1), 0), the output of the ReLU in front of the layer, and gy = N(0, 1) with
+    half of its elements zeroed, a gradient that came back through a ReLU.  Dense N(0, 1) data would leave the slice-aware dW bound
+    too blunt at 256 -> 64 (a missing 32-pixel stage seen on 0.64 of dW; tests/test_conv_train_host.py asks for 3/4): the terms of a
+    sparse sum are larger against their mean absolute value, which is what A measures."""
+    B, H, W, cin, cout, seed = TRAINER[name]
+    M = B * H * W
+    g = torch.Generator().manual_seed(seed)
+    d = dict(x=torch.randn(M, cin, generator=g).clamp_(min=0), w=torch.randn(cout, cin, generator=g) * (1.0 / cin ** 0.5),
+             gy=torch.randn(M, cout, generator=g) * (torch.rand(M, cout, generator=g) < 0.5))
+
+    def gemms(x, w, gy):
+        return dict(y=x @ w.t(), dx=gy @ w, dw=gy.t() @ x)
+    return (d, gemms(d["x"].double(), d["w"].double(), d["gy"].double()),
+            gemms(d["x"].double().abs(), d["w"].double().abs(), d["gy"].double().abs()))
+
+
+def slice_length_bound(M, n):
+    """an upper bound on the length of the weight gradient's slices, from the public slice count n alone: n - 1 full slices of equal
+    length leave at least one pixel to the last, (n - 1) len < M, hence len <= ceil(M / (n - 1)); one slice is all of M"""
+    return M if n <= 1 else -(-M // (n - 1))
 
 
 class Bottleneck(torch.nn.Module):

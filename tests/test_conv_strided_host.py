@@ -10,6 +10,7 @@ torch = pytest.importorskip("torch")
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import conv_strided_ref as ref  # noqa: E402
+import train_common as tc  # noqa: E402
 from test_conv_train_host import _model  # noqa: E402
 
 
@@ -48,6 +49,43 @@ def test_strided_wgrad_slices_and_workspace(L):
         OH, OW = ref.out_hw(H, W, k)
         n = L.ssg_conv_wgrad_strided_num_slices(B * OH * OW, cout, k, k, cin, 2)
         assert n >= 3 and (B * OH * OW) % n != 0
+    # the real-width cases: three slices with a shorter last one, ragged last tiles of 128 output and of 64 input pixels per class
+    for (B, H, W, cin, cout, k, _) in ref.REAL.values():
+        OH, OW = ref.out_hw(H, W, k)
+        M = B * OH * OW
+        assert H % 2 == 0 and W % 2 == 0 and 512 < M < 768 and M % 64 != 0
+        assert L.ssg_conv_wgrad_strided_num_slices(M, cout, k, k, cin, 2) == 3
+
+
+def test_the_bound_sees_a_missing_chunk_stage_or_pixels_at_real_widths():
+    """tests/test_conv_train_host.py's sharpness condition on the stride-2 real-width cases: each of the three mutated float64
+    references (one 32-channel chunk of one tap missing from y, one 32-output-channel stage of one tap from dX, the last 32 output
+    pixels from dW) breaks (L + 2) 2^-24 A on at least 3/4 of the elements it touches; torch's float32 CPU convolution meets the bound"""
+    tc.check_sensitivity(ref.reference, ref.outputs, ref.REAL, 2)
+
+
+def test_strided_packing_restatement():
+    """pack_dgrad_s2 is [tap][Cout][Cin] with tap = r KW + s: element by element on a weight whose value names its index, and as the
+    GEMM operand it is -- dY[oh, ow] wp[tap] added into dX[2 oh + r - 1, 2 ow + s - 1] gives the float64 data gradient"""
+    cout, cin, k = 64, 128, 3
+    idx = torch.arange(cout * cin * k * k, dtype=torch.float64).reshape(cout, cin, k, k)
+    p = ref.pack_dgrad_s2(idx)
+    assert tuple(p.shape) == (k * k, cout, cin) and p.is_contiguous()
+    for (co, ci, r, s) in [(0, 0, 0, 0), (cout - 1, cin - 1, k - 1, k - 1), (33, 35, 1, 0), (5, 63, 0, 2)]:
+        assert float(p[r * k + s, co, ci]) == float(idx[co, ci, r, s])
+    B, H, W, cin, cout, k, seed = ref.CASES["3x3_even"]
+    d, r64, _, _ = ref.reference(*ref.CASES["3x3_even"])
+    wp, gy = ref.pack_dgrad_s2(d["w"].double()), d["gy"].double()
+    OH, OW = ref.out_hw(H, W, k)
+    dx = torch.zeros(B, cin, H, W, dtype=torch.float64)
+    for r in range(k):
+        for s in range(k):
+            for oh in range(OH):
+                for ow in range(OW):
+                    ih, iw = 2 * oh + r - 1, 2 * ow + s - 1
+                    if 0 <= ih < H and 0 <= iw < W:
+                        dx[:, :, ih, iw] += gy[:, :, oh, ow] @ wp[r * k + s]
+    assert float((dx - r64["dx"]).abs().max()) <= 1e-12 * float(r64["dx"].abs().max())
 
 
 def test_bad_shapes_are_refused_before_any_launch(L):

@@ -1,5 +1,6 @@
 """Host half of the train-mode Conv2d tests (no GPU): the index formula of the two weight packings, the pure host functions of the
-weight gradient's slice cut, the argument checks that come before any launch, and use_device_conv on a hand-built model."""
+weight gradient's slice cut, the argument checks that come before any launch, use_device_conv on a hand-built model, and what the
+GPU suite's bounds see of a plausible kernel fault at the real widths (mutated float64 references)."""
 import os
 import sys
 
@@ -9,6 +10,7 @@ torch = pytest.importorskip("torch")
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import conv_train_ref as ref  # noqa: E402
+import train_common as tc  # noqa: E402
 
 
 @pytest.fixture(scope="module")
@@ -61,6 +63,39 @@ def test_wgrad_slices_and_workspace(L):
         assert B is not None and B <= 64
         n = L.ssg_conv_wgrad_num_slices(B * H * W, cout, k, k, cin)
         assert n >= 3 and (B * H * W) % n != 0
+    # the real-width cases: three slices with a shorter last one, a ragged last 128-row tile
+    for (B, H, W, cin, cout, k, _) in ref.REAL.values():
+        M = B * H * W
+        assert 512 < M < 768 and M % 128 != 0 and L.ssg_conv_wgrad_num_slices(M, cout, k, k, cin) == 3
+
+
+def test_the_bound_sees_a_missing_chunk_stage_or_pixels_at_real_widths():
+    """the yardstick of the real-width GPU cases is sharp there: a forward without one 32-channel chunk of one tap, a data gradient
+    without one 32-output-channel stage of one tap and a weight gradient without its last 32 pixels each break (L + 2) 2^-24 A on at
+    least 3/4 of the elements they touch -- a condition on the cases' data and shapes, not a measurement (seen on the CPU: 0.90 ... 1.00);
+    torch's float32 CPU convolution meets the same bound everywhere"""
+    tc.check_sensitivity(ref.reference, ref.outputs, ref.REAL, 1)
+
+
+@pytest.mark.parametrize("name", sorted(ref.TRAINER))
+def test_the_slice_aware_bound_sees_a_missing_stage_at_the_trainers_batch(L, name):
+    """the dW bound of test_gpu_conv_train.py::test_trainer_batch_1x1_against_float64_matmul, (L_s + 2) 2^-24 A with L_s the slice
+    length bound from the public slice count, against a weight gradient without one 32-pixel stage (the last of the first slice):
+    broken on at least 3/4 of dW; the usual (M + 2) 2^-24 A would not notice"""
+    B, H, W, cin, cout, _ = ref.TRAINER[name]
+    M = B * H * W
+    d, r64, A = ref.gemm_reference(name)
+    n = L.ssg_conv_wgrad_num_slices(M, cout, 1, 1, cin)
+    Ls = ref.slice_length_bound(M, n)
+    assert n >= 256 and 256 <= Ls <= 2 * M // n + 2
+    gm = d["gy"].double()
+    m0 = (M // n) // 32 * 32 - 32                                     # inside the first slice, whatever the cut
+    gm[m0:m0 + 32] = 0
+    delta = (gm.t() @ d["x"].double() - r64["dw"]).abs()
+    seen = float((delta > ref.bound(Ls, A["dw"])).double().mean())
+    blind = float((delta > ref.bound(M, A["dw"])).double().mean())
+    print("%s: n = %d, L_s = %d, seen by the slice-aware bound %.3f, by (M + 2) 2^-24 A %.3f" % (name, n, Ls, seen, blind))
+    assert seen >= 0.75 and blind == 0.0
 
 
 def test_bad_shapes_are_refused_before_any_launch(L):

@@ -41,6 +41,8 @@ CASES = {
     "aligned_cl": ((4, 64, 8, 4), True, None, 104),
     "wide_c": ((5, 70, 3, 3), False, None, 105),             # C > 64 and no multiple of 64
     "wide_c_cl": ((2, 260, 3, 2), True, None, 109),          # channel contiguous, four channels per lane, two column tiles
+    "real_c1024_cl": ((3, 1024, 4, 8), True, None, 111),     # layer3's width: four column tiles of 256 channels
+    "real_c2048_cl": ((5, 2048, 2, 4), True, None, 112),     # layer4's width: eight column tiles
     "multi_partial": ((33, 8, 16, 8), False, None, 106),     # the smallest N at which a channel is split over two workgroups
     "large_mean": ((4, 6, 8, 4), False, "large_mean", 107),  # x = 1000 + N(0, 1): cancellation in the variance
     "const_channel": ((3, 5, 7, 5), False, "const", 108),    # var = 0, invstd = eps^-1/2

@@ -9,6 +9,10 @@ Accuracy criterion, derived and not measured (the one of test_gpu_conv_train.py)
 with L the length of that output's reduction (KH KW Cin for y, KH KW Cout for dX -- an upper bound for every parity class -- and
 B OH OW for dW) and A the same operator applied to |x|, |w|, |dY| in float64.
 
+The cases: the smallest shapes at which each thing can go wrong (CASES, MULTI) and the six stride-2 convolutions of ResNet-50 at their
+real channel pairs and input row widths, with just enough pixels for three weight-gradient slices and two 64-pixel tiles per parity
+class of dX (REAL: up to 1024 -> 2048, K up to 4608; tests/test_conv_strided_host.py shows what the bound sees there).
+
 Composition (use_device_conv(strided=True) + use_device_batchnorm on a stride-2 bottleneck): test_gpu_conv_train.py's criterion on the
 parameter gradients,
 
@@ -43,6 +47,8 @@ def _case(name):
     """the (B, H, W, Cin, Cout, k, seed) of a named case; the multi-slice ones take the smallest B that gives three ragged slices"""
     if name in ref.CASES:
         return ref.CASES[name]
+    if name in ref.REAL:
+        return ref.REAL[name]
     H, W, cin, cout, k, seed = ref.MULTI[name]
     B = ref.multi_slice_batch(_lib(), H, W, cin, cout, k)
     # a slice rule with a floor that hides stage 2 from this suite must be changed, not tested around
@@ -50,7 +56,7 @@ def _case(name):
     return (B, H, W, cin, cout, k, seed)
 
 
-ALL = tuple(ref.CASES) + tuple(ref.MULTI)
+ALL = tuple(ref.CASES) + tuple(ref.MULTI) + tuple(ref.REAL)
 
 
 def _outs(case):
@@ -142,7 +148,7 @@ def test_entry_points_against_float64(name):
     else:
         from conv_train_ref import pack_fwd
         assert torch.equal(got["w_fwd"], pack_fwd(w))
-        assert torch.equal(got["w_dgrad"], w.permute(2, 3, 0, 1).reshape(k * k, cout, cin))
+        assert torch.equal(got["w_dgrad"], ref.pack_dgrad_s2(w))
     api = _api(case)
     for o in _outs(case):                                   # the autograd function adds nothing of its own
         assert torch.equal(api[o].cpu(), got[o]), o
@@ -151,7 +157,10 @@ def test_entry_points_against_float64(name):
 def test_1x1_even_sides_are_exact_zeros():
     """what no tap of a stride-2 1x1 reaches -- the three empty parity classes, the last row and column of an even-sized input -- is
     written, and as exactly 0.0, by both routes"""
-    case = ref.CASES["1x1_even"]
+    _exact_zeros(ref.CASES["1x1_even"])
+
+
+def _exact_zeros(case):
     for dx in (_api(case)["dx"].cpu(), _abi(case)["dx"]):
         live = torch.zeros(dx.shape[2:], dtype=torch.bool)
         live[0::2, 0::2] = True
@@ -159,6 +168,29 @@ def test_1x1_even_sides_are_exact_zeros():
         dead = dx[:, :, ~live]
         assert bool((dead == 0).all()) and not bool(torch.signbit(dead).any())
         assert bool((dx[:, :, live] != 0).any())
+
+
+@pytest.mark.parametrize("name", ref.DOWNSAMPLE)
+def test_downsample_empty_classes_are_exact_zeros(name):
+    """the same property on ResNet-50's three downsample shapes: 4 to 16 column tiles of dX, three of four classes without a tap"""
+    _exact_zeros(ref.REAL[name])
+
+
+def test_real_cases_have_three_slices_and_ragged_tiles():
+    """every real-width case: exactly three weight-gradient slices of which the last is shorter (from the library's own count, so a
+    later change of the plan cannot quietly turn these into one-slice cases), a ragged last 128-row tile in the forward, and, the
+    sides being even, four parity classes of M pixels each: at least two 64-pixel tiles, the last one ragged"""
+    L = _lib()
+    for name, (B, H, W, cin, cout, k, _) in ref.REAL.items():
+        assert H % 2 == 0 and W % 2 == 0, name
+        OH, OW = ref.out_hw(H, W, k)
+        M = B * OH * OW
+        assert (OH, OW) == (H // 2, W // 2) and 512 < M < 768 and M % 256 != 0 and M % 128 != 0, name
+        assert M == B * ((H + 1) // 2) * ((W + 1) // 2) and M > 64 and M % 64 != 0, name       # the largest class of dX
+        n = L.ssg_conv_wgrad_strided_num_slices(M, cout, k, k, cin, 2)
+        assert n == 3 and M % n != 0, (name, n)             # equal slices cannot cover M: the last one is shorter
+        assert L.ssg_conv_wgrad_strided_workspace_bytes(M, cout, k, k, cin, 2) == 4 * 3 * cout * k * k * cin
+    assert sorted(c[3:6] for c in ref.REAL.values()) == [(128, 128, 3), (256, 256, 3), (256, 512, 1), (512, 512, 3), (512, 1024, 1), (1024, 2048, 1)]
 
 
 def test_multi_slice_cases_have_a_real_slice_sum():

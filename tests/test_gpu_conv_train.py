@@ -8,6 +8,12 @@ Accuracy criterion, derived and not measured: every element of every output sati
 with L the length of that output's reduction (KH KW Cin for y, KH KW Cout for dX, B OH OW for dW) and A the same convolution or gradient
 applied to |x|, |w|, |dY| in float64: the standard bound of a length-L float32 sum in any order, plus one rounding.
 
+The cases: the smallest shapes at which each thing can go wrong (CASES, MULTI: 64 ... 192 channels, sides up to 8), every distinct
+(Cin, Cout, k) of ResNet-50 on its real row width with just enough pixels for three weight-gradient slices (REAL: up to 2048 channels,
+K up to 4608), and layer1's two 1x1 shapes at the trainer's own M = 131072 against float64 matmuls, dW under the tighter slice-aware
+bound derived in test_trainer_batch_1x1_against_float64_matmul (TRAINER).  tests/test_conv_train_host.py shows that both bounds see
+a missing 32-wide chunk, stage or pixel group at these shapes.
+
 Composition (use_device_conv + use_device_batchnorm on a bottleneck block): each BatchNorm divides by a batch standard deviation, so
 the per-element bound does not carry through; the criterion is test_gpu_batchnorm.py's form, on the parameter gradients,
 
@@ -42,6 +48,8 @@ def _case(name):
     """the (B, H, W, Cin, Cout, k, seed) of a named case; the multi-slice ones take the smallest B that gives three slices"""
     if name in ref.CASES:
         return ref.CASES[name]
+    if name in ref.REAL:
+        return ref.REAL[name]
     H, W, cin, cout, k, seed = ref.MULTI[name]
     B = ref.multi_slice_batch(_lib(), H, W, cin, cout, k)
     # a slice rule with a floor that hides stage 2 from this suite must be changed, not tested around
@@ -49,7 +57,7 @@ def _case(name):
     return (B, H, W, cin, cout, k, seed)
 
 
-ALL = tuple(ref.CASES) + tuple(ref.MULTI)
+ALL = tuple(ref.CASES) + tuple(ref.MULTI) + tuple(ref.REAL)
 
 
 def _api(case, x_cl=True, w_cl=False, x_grad=True, w_grad=True):
@@ -126,6 +134,88 @@ def test_multi_slice_cases_have_a_real_slice_sum():
         n = L.ssg_conv_wgrad_num_slices(B * H * W, cout, k, k, cin)
         assert n >= 3 and (B * H * W) % n != 0             # equal slices cannot cover M: the last one is shorter
         assert L.ssg_conv_wgrad_num_slices((B - 1) * H * W, cout, k, k, cin) < 3
+
+
+def test_real_cases_have_three_slices_and_ragged_tiles():
+    """every real-width case: exactly three weight-gradient slices of which the last is shorter (from the library's own count, so a
+    later change of the plan cannot quietly turn these into one-slice cases), and a ragged last 128-row tile in the forward and in
+    the data gradient"""
+    L = _lib()
+    pairs = set()
+    for name, (B, H, W, cin, cout, k, _) in ref.REAL.items():
+        M = B * H * W
+        assert 512 < M < 768 and M % 256 != 0 and M % 128 != 0, name
+        n = L.ssg_conv_wgrad_num_slices(M, cout, k, k, cin)
+        assert n == 3 and M % n != 0, (name, n)             # equal slices cannot cover M: the last one is shorter
+        assert L.ssg_conv_wgrad_workspace_bytes(M, cout, k, k, cin) == 4 * 3 * cout * k * k * cin
+        pairs.add((cin, cout, k))
+    assert len(pairs) == len(ref.REAL) == 16 and max(p[0] for p in pairs) == 2048 and max(p[1] for p in pairs) == 2048
+
+
+def _abi_gemm(name):
+    """a TRAINER case through the raw entry points -> ({y, dx, dw} on the device in NHWC / [Cout, Cin], slice count n); the workspace
+    is checked against its NaN guard"""
+    from ssg_amd._lib import check, ptr, stream
+    L = _lib()
+    B, H, W, cin, cout, _ = ref.TRAINER[name]
+    M = B * H * W
+    d = ref.gemm_reference(name)[0]
+    x, gy, w = d["x"].cuda(), d["gy"].cuda(), d["w"].cuda().view(cout, cin, 1, 1)
+    wf, wd = _nan(cout, cin), _nan(cin, cout)
+    s = w.stride()
+    check(L.ssg_conv_pack_train_f32(ptr(w), s[0], s[1], s[2], s[3], cout, cin, 1, 1, ptr(wf), ptr(wd), stream()), "pack")
+    zeros = torch.zeros(max(cin, cout), dtype=torch.float32, device="cuda")
+    y, dx, dw = _nan(M, cout), _nan(M, cin), _nan(cout, cin, 1, 1)
+    check(L.ssg_conv2d_nhwc_f32(ptr(x), ptr(wf), ptr(zeros), None, ptr(y), B, H, W, cin, cout, 1, 1, 1, 0, 0, stream()), "forward")
+    check(L.ssg_conv2d_nhwc_f32(ptr(gy), ptr(wd), ptr(zeros), None, ptr(dx), B, H, W, cout, cin, 1, 1, 1, 0, 0, stream()), "dgrad")
+    n = L.ssg_conv_wgrad_num_slices(M, cout, 1, 1, cin)
+    nws = L.ssg_conv_wgrad_workspace_bytes(M, cout, 1, 1, cin)
+    assert n >= 1 and nws == 4 * n * cout * cin
+    ws = _nan(nws // 4 + 64)                               # 64 floats of guard behind the workspace
+    s = dw.stride()
+    check(L.ssg_conv_wgrad_f32(ptr(gy), ptr(x), B, H, W, cin, cout, 1, 1, ptr(dw), s[0], s[1], s[2], s[3], ptr(ws), nws, 3, stream()), "wgrad")
+    torch.cuda.synchronize()
+    assert bool(torch.isnan(ws[nws // 4:]).all()) and not bool(torch.isnan(ws[:nws // 4]).any())     # all of the workspace, nothing past it
+    return dict(y=y, dx=dx, dw=dw.view(cout, cin)), n
+
+
+def _gemm_rows(name, got, n):
+    """[(output, L, max |dev - ref64|, worst err / bound)] of a TRAINER case: L = Cin for y, Cout for dx, the slice length bound for dw"""
+    B, H, W, cin, cout, _ = ref.TRAINER[name]
+    _, r64, A = ref.gemm_reference(name)
+    rows = []
+    for o, L in (("y", cin), ("dx", cout), ("dw", ref.slice_length_bound(B * H * W, n))):
+        g = got[o].cpu().double()
+        assert g.shape == r64[o].shape and bool(torch.isfinite(g).all()), o
+        err = (g - r64[o]).abs()
+        rows.append((o, L, float(err.max()), float((err / ref.bound(L, A[o]).clamp_min(1e-300)).max())))
+    return rows
+
+
+@pytest.mark.parametrize("name", sorted(ref.TRAINER))
+def test_trainer_batch_1x1_against_float64_matmul(name):
+    """layer1's two 1x1 shapes at the trainer's own B = 64, 64 x 32 pixels: M = 131072, hundreds of slices and a grid.z to match.  A
+    1x1 convolution is a GEMM, so the reference is float64 matmuls (conv_train_ref.gemm_reference).
+
+    y and dX: the usual (L + 2) 2^-24 A.  dW: (M + 2) 2^-24 A would be about 500 times looser than what the kernel's documented
+    structure gives -- float32 partial sums over one slice each, the slices added in float64, one rounding.  A slice's partial sum
+    errs by at most len 2^-24 A_slice, the A_slice add up to A, the float64 sum adds nothing visible and the rounding 2^-24 A, so
+
+        |dW - ref64| <= (L_s + 2) 2^-24 A,   L_s = ceil(M / (n - 1)) >= len
+
+    because n - 1 full slices of len pixels leave at least one pixel to the last: (n - 1) len < M.  n is the public slice count
+    (ssg_conv_wgrad_num_slices); no constant of the kernel enters.  Also: the workspace is 4 n Cout K bytes, all of it and nothing
+    behind it is written, and a second run gives the same bits."""
+    B, H, W, cin, cout, _ = ref.TRAINER[name]
+    got, n = _abi_gemm(name)
+    assert n >= 256 and n == _lib().ssg_conv_wgrad_workspace_bytes(B * H * W, cout, 1, 1, cin) // (4 * cout * cin)
+    for o, L, err, worst in _gemm_rows(name, got, n):
+        print("%s %s: n = %d slices, L = %d, max |dev - ref64| = %.3g, worst err / bound = %.3g" % (name, o, n, L, err, worst))
+        assert worst <= 1.0, "%s: %s misses (L + 2) 2^-24 A with L = %d by a factor of %.3g" % (name, o, L, worst)
+    again, n2 = _abi_gemm(name)
+    assert n2 == n
+    for o in OUTS:
+        assert torch.equal(again[o], got[o]), (name, o)
 
 
 def test_layouts_give_the_same_bits():
@@ -248,4 +338,11 @@ def measure():
     for name in ALL:
         case = _case(name)
         rows += tc.bound_rows(ref.reference, ref.outputs, name, case, (("conv2d_train", _api(case)), ("entry points", _abi(case))), OUTS)
+    for name in sorted(ref.TRAINER):                        # the float32 CPU column: the same three matmuls in float32; dw against the slice-aware bound
+        B, H, W, cin, cout, _ = ref.TRAINER[name]
+        d, r64, _ = ref.gemm_reference(name)
+        f32 = dict(y=d["x"] @ d["w"].t(), dx=d["gy"] @ d["w"], dw=d["gy"].t() @ d["x"])
+        got, n = _abi_gemm(name)
+        for o, _, err, worst in _gemm_rows(name, got, n):
+            rows.append((name, (B, H, W, cin, cout, 1), "entry points", o, err, float((f32[o].double() - r64[o]).abs().max()), worst))
     return rows

@@ -1,6 +1,6 @@
 """What the train-mode suites (tests/test_gpu_conv_train.py, test_gpu_conv_strided.py, test_gpu_head.py) and their yardsticks
 (tests/conv_train_ref.py, conv_strided_ref.py, head_ref.py) share: the unit roundoff and the derived bound, the handles on the library,
-and the composition harness (a model whose ReLU inputs stay away from 0, its parameter gradients, and the criterion
+the mutated references that show what the bound can see (`sensitivity`, host only), and the composition harness (a model whose ReLU inputs stay away from 0, its parameter gradients, and the criterion
 
     err(device) <= F_COMP * err(float32 CPU run) + 2^-24,   err(v) = max |v - ref64| / max |ref64|
 
@@ -54,6 +54,78 @@ def bound_rows(reference, outputs, name, case, routes, outs):
             rows.append((name, case[:6], path, o, float(err.max()), float((f32[o].double() - r64[o]).abs().max()),
                          float((err / bound(L[o], A[o]).clamp_min(1e-300)).max())))
     return rows
+
+
+# ---- what the bound can see --------------------------------------------------------------------------------------------------------------
+
+def tap_reach(B, H, W, k, stride):
+    """[k, k, B, OH, OW] bool: tap (r, s) of output pixel (b, oh, ow) reads inside the H x W image (padding k // 2)"""
+    p = k // 2
+    OH, OW = (H + 2 * p - k) // stride + 1, (W + 2 * p - k) // stride + 1
+    ih = torch.arange(OH)[None, :] * stride + torch.arange(k)[:, None] - p                 # [k, OH]
+    iw = torch.arange(OW)[None, :] * stride + torch.arange(k)[:, None] - p                 # [k, OW]
+    ok = ((ih >= 0) & (ih < H))[:, None, :, None] & ((iw >= 0) & (iw < W))[None, :, None, :]
+    return ok[:, :, None].expand(k, k, B, OH, OW)
+
+
+def tap_hits(H, W, k, stride, r, s):
+    """[H, W] bool: the input pixels that tap (r, s) of some output pixel reads (ih = oh stride + r - k // 2 with 0 <= oh < OH)"""
+    p = k // 2
+    OH, OW = (H + 2 * p - k) // stride + 1, (W + 2 * p - k) // stride + 1
+    th, tw = torch.arange(H) + p - r, torch.arange(W) + p - s
+    ok_h = (th >= 0) & (th % stride == 0) & (th // stride < OH)
+    ok_w = (tw >= 0) & (tw % stride == 0) & (tw // stride < OW)
+    return ok_h[:, None] & ok_w[None, :]
+
+
+def sensitivity(reference, case, stride):
+    """How much of a plausible kernel fault the bound (L + 2) 2^-24 A sees.  Three mutated float64 references of `reference(*case)`:
+        y   one 32-channel chunk of one tap missing from the weight        (the last chunk of the last tap)
+        dx  one stage of 32 output channels of one tap missing             (the last 32 output channels of the last tap)
+        dw  the last 32 output pixels missing
+    -> {output: (fraction of the touched elements on which |mutated - ref64| > bound, number of touched elements)}; an element is
+    touched when the missing terms include one that reads inside the image."""
+    from torch.nn import grad as G
+    B, H, W, cin, cout, k, _ = case
+    d, r64, A, L = reference(*case)
+    x, w, gy, pad = d["x"].double(), d["w"].double(), d["gy"].double(), d["pad"]
+    r = s = k - 1
+    reach = tap_reach(B, H, W, k, stride)
+    mut, touched = {}, {}
+    wm = w.clone()
+    wm[:, cin - 32:, r, s] = 0
+    mut["y"] = torch.nn.functional.conv2d(x, wm, None, stride, pad)
+    touched["y"] = reach[r, s][:, None].expand_as(r64["y"])
+    wm = w.clone()
+    wm[cout - 32:, :, r, s] = 0
+    mut["dx"] = G.conv2d_input(x.shape, wm, gy, stride, pad)
+    touched["dx"] = tap_hits(H, W, k, stride, r, s)[None, None].expand_as(r64["dx"])
+    gm = gy.permute(0, 2, 3, 1).contiguous()                                               # [B, OH, OW, Cout]: pixels in the kernels' order
+    gm.view(-1, cout)[-32:] = 0
+    mut["dw"] = G.conv2d_weight(x, w.shape, gm.permute(0, 3, 1, 2), stride, pad)
+    touched["dw"] = reach.reshape(k, k, -1)[:, :, -32:].any(2)[None, None].expand_as(r64["dw"])
+    out = {}
+    for o in ("y", "dx", "dw"):
+        assert mut[o].shape == r64[o].shape and bool(touched[o].any()), o
+        seen = (mut[o] - r64[o]).abs() > bound(L[o], A[o])
+        assert not bool(seen[~touched[o]].any()), o                                          # the untouched elements did not move
+        out[o] = (float(seen[touched[o]].double().mean()), int(touched[o].sum()))
+    return out
+
+
+def check_sensitivity(reference, outputs, cases, stride, need=0.75):
+    """every case: each mutation of `sensitivity` breaks the bound on at least `need` of the elements it touches, and torch's float32
+    CPU convolution (a correct float32 implementation) meets the bound everywhere"""
+    for name, case in cases.items():
+        d, r64, A, L = reference(*case)
+        f32 = outputs(d["x"], d["w"], d["gy"], d["pad"], torch.float32)
+        fr = sensitivity(reference, case, stride)
+        ok32 = {o: float(((f32[o].double() - r64[o]).abs() / bound(L[o], A[o]).clamp_min(1e-300)).max()) for o in fr}
+        print("%-22s %-28s seen: y %.3f dx %.3f dw %.3f   float32 CPU err / bound: y %.3g dx %.3g dw %.3g"
+              % (name, case[:6], fr["y"][0], fr["dx"][0], fr["dw"][0], ok32["y"], ok32["dx"], ok32["dw"]))
+        for o in fr:
+            assert fr[o][0] >= need, (name, o, fr[o])
+            assert ok32[o] <= 1.0, (name, o, ok32[o])
 
 
 # ---- composition -----------------------------------------------------------------------------------------------------------------------

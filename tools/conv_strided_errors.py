@@ -24,11 +24,13 @@ def main():
     lines = ["strided train-mode Conv2d, 7x7 stem and MaxPool2d(3, 2, 1) (csrc/conv_strided.hip) on %s: error against torch's autograd in float64 "
              "on the CPU" % torch.cuda.get_device_name(0),
              "err = max |v - ref64| (absolute); err / bound = worst element of |dev - ref64| / ((L + 2) 2^-24 A), asserted <= 1",
-             "%-13s %-26s %-21s %-3s %11s %11s %12s" % ("case", "(B, H, W, Cin, Cout, k)", "via", "out", "err_dev", "err_f32cpu", "err / bound")]
-    worst = 0.0
+             "%-18s %-28s %-21s %-3s %11s %11s %12s" % ("case", "(B, H, W, Cin, Cout, k)", "via", "out", "err_dev", "err_f32cpu", "err / bound")]
+    worst = worst_new = 0.0
     for name, case, path, o, e_dev, e_f32, frac in t.measure():
         worst = max(worst, frac)
-        lines.append("%-13s %-26s %-21s %-3s %11.3e %11.3e %12.3g" % (name, case, path, o, e_dev, e_f32, frac))
+        if name.startswith("real_"):
+            worst_new = max(worst_new, frac)
+        lines.append("%-18s %-28s %-21s %-3s %11.3e %11.3e %12.3g" % (name, case, path, o, e_dev, e_f32, frac))
     lines.append("worst err / bound: %.3g" % worst)
     lines.append("")
     lines.append("max-pool backward: err / bound = worst element of |dX - ref64| / ((4 + 2) 2^-24 A); the forward is bit-equal (asserted)")
@@ -38,12 +40,14 @@ def main():
             y, dx = route(name)
             err = (dx.cpu().double() - dx64).abs()
             frac = float((err / ((4 + 2) * ref.U * A).clamp_min(1e-300)).max())
-            lines.append("%-13s %-26s %-21s %-3s %11.3e %11s %12.3g" % (name, tuple(x.shape), route.__name__.strip("_"), "dx", float(err.max()), "-", frac))
+            lines.append("%-18s %-28s %-21s %-3s %11.3e %11s %12.3g" % (name, tuple(x.shape), route.__name__.strip("_"), "dx", float(err.max()), "-", frac))
     lines.append("")
     lines.append("composition: Bottleneck(256 -> 512, stride 2) with use_device_conv(strided=True) + use_device_batchnorm, x %r, parameter gradients"
                  % (t.COMP_SHAPE,))
     lines.append("err = max |v - ref64| / max |ref64|; ratio = err_dev / err_f32 (float32 CPU run of the same block)")
     lines += composition_table(t.measure_composition(), t.F_COMP, 24)
+    lines.append("")
+    lines.append("worst err / bound of the real-width cases (real_*): %.3g" % worst_new)
     with open(out, "w") as f:
         f.write("\n".join(lines) + "\n")
     print("\n".join(lines))
