@@ -27,10 +27,7 @@ using bneck::v16f;
 using bneck::v4u;
 using bneck::v8h;
 using bneck::v4f;
-using bneck::encode4;
-using bneck::decode4;
 using bneck::relu4;
-using bneck::hi_nonfinite_bits;
 
 struct Params {
   const float* x; float* out;
@@ -160,8 +157,8 @@ __global__ __launch_bounds__(NTHR, 1) void basicblock_kernel(Params p) {
       v = relu4(v);
       if (!inside) v = make_float4(0.f, 0.f, 0.f, 0.f);
       uint2 hi, lo;
-      encode4(v, hi, lo);
-      ovf |= hi_nonfinite_bits(hi);
+      split_encode4(v, hi, lo);
+      ovf |= split_hi_nonfinite_bits(hi);
       unsigned char* d = smem + Y_OFF + (yr * IW + l32) * PY + (ch >> 3) * 32 + h * 8;
       *reinterpret_cast<uint2*>(d) = hi; *reinterpret_cast<uint2*>(d + 16) = lo;
     }
@@ -227,12 +224,12 @@ __global__ __launch_bounds__(NTHR, 1) void basicblock_kernel(Params p) {
       const float4 cs = cs2r[j][q], bi = b2r[j][q];
       float4 v = make_float4(acc2[j][4 * q] * cs.x + bi.x, acc2[j][4 * q + 1] * cs.y + bi.y, acc2[j][4 * q + 2] * cs.z + bi.z, acc2[j][4 * q + 3] * cs.w + bi.w);
       const unsigned char* rs = xrow + (ch >> 3) * 32 + h * 8;
-      const float4 r4 = decode4(*reinterpret_cast<const uint2*>(rs), *reinterpret_cast<const uint2*>(rs + 16));
+      const float4 r4 = split_decode4(*reinterpret_cast<const uint2*>(rs), *reinterpret_cast<const uint2*>(rs + 16));
       v.x += r4.x; v.y += r4.y; v.z += r4.z; v.w += r4.w;
       v = relu4(v);
       uint2 hi, lo;
-      encode4(v, hi, lo);
-      ovf |= hi_nonfinite_bits(hi);
+      split_encode4(v, hi, lo);
+      ovf |= split_hi_nonfinite_bits(hi);
       unsigned char* d = orow + l32 * PY + (ch >> 3) * 32 + h * 8;
       *reinterpret_cast<uint2*>(d) = hi; *reinterpret_cast<uint2*>(d + 16) = lo;
     }

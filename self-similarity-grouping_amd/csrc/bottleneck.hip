@@ -90,24 +90,7 @@ struct Cfg {
   static_assert(LDS <= 80 * 1024, "two workgroups per CU");
 };
 
-__device__ __forceinline__ unsigned pack2(_Float16 a, _Float16 b) {
-  return (unsigned)__builtin_bit_cast(unsigned short, a) | ((unsigned)__builtin_bit_cast(unsigned short, b) << 16);
-}
-__device__ __forceinline__ void encode4(const float4 v, uint2& hi, uint2& lo) {
-  const _Float16 h0 = (_Float16)v.x, h1 = (_Float16)v.y, h2 = (_Float16)v.z, h3 = (_Float16)v.w;
-  hi = make_uint2(pack2(h0, h1), pack2(h2, h3));
-  lo = make_uint2(pack2((_Float16)(v.x - (float)h0), (_Float16)(v.y - (float)h1)), pack2((_Float16)(v.z - (float)h2), (_Float16)(v.w - (float)h3)));
-}
-// bits 15 / 31 of the result are set when a hi half is infinite or NaN (exponent field all ones: + 0x0400 carries into the sign
-// position, nothing smaller does); OR-accumulated over the kernel and tested once at the end
-__device__ __forceinline__ unsigned hi_nonfinite_bits(const uint2 hi) {
-  return ((hi.x & 0x7c007c00u) + 0x04000400u) | ((hi.y & 0x7c007c00u) + 0x04000400u);
-}
-__device__ __forceinline__ float hlo(unsigned u) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(u & 0xffffu)); }
-__device__ __forceinline__ float hhi(unsigned u) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(u >> 16)); }
-__device__ __forceinline__ float4 decode4(const uint2 hi, const uint2 lo) {
-  return make_float4(hlo(hi.x) + hlo(lo.x), hhi(hi.x) + hhi(lo.x), hlo(hi.y) + hlo(lo.y), hhi(hi.y) + hhi(lo.y));
-}
+// (the split-half codec -- split_encode4, split_pair_decode4, split_pair_pack, split_hi_nonfinite_bits -- is ssg_common.h's)
 __device__ __forceinline__ float4 relu4(float4 v) {
   return make_float4(v.x > 0.f ? v.x : 0.f, v.y > 0.f ? v.y : 0.f, v.z > 0.f ? v.z : 0.f, v.w > 0.f ? v.w : 0.f);
 }
@@ -272,8 +255,8 @@ __global__ __launch_bounds__(256, 2) void bottleneck_kernel(Params p) {
         v = relu4(v);
         if (!inside) v = make_float4(0.f, 0.f, 0.f, 0.f);
         uint2 hi, lo;
-        encode4(v, hi, lo);
-        ovf |= hi_nonfinite_bits(hi);
+        split_encode4(v, hi, lo);
+        ovf |= split_hi_nonfinite_bits(hi);
         unsigned char* d = smem + (hp0 + l32) * K::PY + (ch >> 3) * 32 + h * 8;
         *reinterpret_cast<uint2*>(d) = hi; *reinterpret_cast<uint2*>(d + 16) = lo;
       }
@@ -380,8 +363,8 @@ __global__ __launch_bounds__(256, 2) void bottleneck_kernel(Params p) {
       float4 v = make_float4(acc2[j][4 * q] * cs.x + bi.x, acc2[j][4 * q + 1] * cs.y + bi.y, acc2[j][4 * q + 2] * cs.z + bi.z, acc2[j][4 * q + 3] * cs.w + bi.w);
       v = relu4(v);
       uint2 hi, lo;
-      encode4(v, hi, lo);
-      ovf |= hi_nonfinite_bits(hi);
+      split_encode4(v, hi, lo);
+      ovf |= split_hi_nonfinite_bits(hi);
       unsigned char* d = myrows + l32 * K::PY + (ch >> 3) * 32 + h * 8;
       *reinterpret_cast<uint2*>(d) = hi; *reinterpret_cast<uint2*>(d + 16) = lo;
     }
@@ -457,17 +440,17 @@ __global__ __launch_bounds__(256, 2) void bottleneck_kernel(Params p) {
       float4 r4;                                                                                                     \
       {   /* even lane holds hi0..7 of the 8-channel group, odd lane lo0..7; each needs hi and lo of ITS four channels */ \
         const unsigned a0 = __float_as_uint(rw.x), a1 = __float_as_uint(rw.y), a2 = __float_as_uint(rw.z), a3 = __float_as_uint(rw.w); \
-        const unsigned g0 = lane_xor1((odd ? a0 : a2)), g1 = lane_xor1((odd ? a1 : a3));                             \
-        const unsigned h0 = odd ? g0 : a0, h1 = odd ? g1 : a1, l0 = odd ? a2 : g0, l1 = odd ? a3 : g1;               \
-        r4 = decode4(make_uint2(h0, h1), make_uint2(l0, l1));                                                        \
+        const unsigned h0 = lane_pair_merge(a0, a2, odd), h1 = lane_pair_merge(a1, a3, odd);                         \
+        const unsigned l0 = lane_pair_merge(a2, a0, !odd), l1 = lane_pair_merge(a3, a1, !odd);                       \
+        r4 = split_decode4(make_uint2(h0, h1), make_uint2(l0, l1));                                                  \
       }                                                                                                              \
       v.x += r4.x; v.y += r4.y; v.z += r4.z; v.w += r4.w;                                                            \
       v = relu4(v);                                                                                                  \
       uint2 hp, lp;                                                                                                  \
-      encode4(v, hp, lp);                                                                                            \
-      ovf |= hi_nonfinite_bits(hp);                                                                                  \
-      const unsigned rx = lane_xor1((odd ? hp.x : lp.x)), ry = lane_xor1((odd ? hp.y : lp.y));                       \
-      const v4u sv_ = {odd ? rx : hp.x, odd ? ry : hp.y, odd ? lp.x : rx, odd ? lp.y : ry};                          \
+      split_encode4(v, hp, lp);                                                                                      \
+      ovf |= split_hi_nonfinite_bits(hp);                                                                            \
+      const uint4 pk = split_pair_pack(hp, lp, odd);                                                                 \
+      const v4u sv_ = {pk.x, pk.y, pk.z, pk.w};                                                                      \
       *reinterpret_cast<v4u*>(patch + pr * EP + chunk * 4) = sv_;   /* lanes 2g, 2g + 1: hi x 8 | lo x 8 of channel group g */ \
       if (p.out) __builtin_amdgcn_raw_buffer_store_b128(sv_, orsrc, tpo, (it * RPI * C + ct_ * 32) * 4, AUX_NT);       \
       if (p.out_s2) __builtin_amdgcn_raw_buffer_store_b128(sv_, srsrc, s2o, (it * (RPI / 2) * C + ct_ * 32) * 4, AUX_NT); \
@@ -522,10 +505,10 @@ __global__ __launch_bounds__(256, 2) void bottleneck_kernel(Params p) {
         v.x = v.x * cs.x + bias.x; v.y = v.y * cs.y + bias.y; v.z = v.z * cs.z + bias.z; v.w = v.w * cs.w + bias.w;
         v = relu4(v);
         uint2 hp, lp;
-        encode4(v, hp, lp);
-        ovf |= hi_nonfinite_bits(hp);
-        const unsigned rx = lane_xor1((odd ? hp.x : lp.x)), ry = lane_xor1((odd ? hp.y : lp.y));
-        *reinterpret_cast<uint4*>(ynp + (int64_t)pr * MIDN + col) = make_uint4(odd ? rx : hp.x, odd ? ry : hp.y, odd ? lp.x : rx, odd ? lp.y : ry);
+        split_encode4(v, hp, lp);
+        ovf |= split_hi_nonfinite_bits(hp);
+        const uint4 pk = split_pair_pack(hp, lp, odd);
+        *reinterpret_cast<uint4*>(ynp + (int64_t)pr * MIDN + col) = pk;
       }
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     }
@@ -564,8 +547,8 @@ __global__ __launch_bounds__(256, 2) void bottleneck_kernel(Params p) {
       float4 v = make_float4(acc2[j][4 * q] * cs.x + bi.x, acc2[j][4 * q + 1] * cs.y + bi.y, acc2[j][4 * q + 2] * cs.z + bi.z, acc2[j][4 * q + 3] * cs.w + bi.w);
       v = relu4(v);
       uint2 hi, lo;
-      encode4(v, hi, lo);
-      ovf |= hi_nonfinite_bits(hi);
+      split_encode4(v, hi, lo);
+      ovf |= split_hi_nonfinite_bits(hi);
       unsigned char* d = smem + (wave * 32 + l32) * K::PY + (ch >> 3) * 32 + h * 8;
       *reinterpret_cast<uint2*>(d) = hi; *reinterpret_cast<uint2*>(d + 16) = lo;
     }
@@ -661,18 +644,17 @@ __global__ __launch_bounds__(256, 2) void bottleneck_kernel(Params p) {
       {   // even lane holds hi0..7 of the 8-channel group, odd lane lo0..7; each needs hi and lo of ITS four channels
         // (component-wise selects: a select between uint2 / float4 aggregates goes through scratch memory)
         const unsigned a0 = __float_as_uint(rw.x), a1 = __float_as_uint(rw.y), a2 = __float_as_uint(rw.z), a3 = __float_as_uint(rw.w);
-        const unsigned g0 = lane_xor1((odd ? a0 : a2)), g1 = lane_xor1((odd ? a1 : a3));
-        const unsigned h0 = odd ? g0 : a0, h1 = odd ? g1 : a1, l0 = odd ? a2 : g0, l1 = odd ? a3 : g1;
-        r4 = decode4(make_uint2(h0, h1), make_uint2(l0, l1));
+        const unsigned h0 = lane_pair_merge(a0, a2, odd), h1 = lane_pair_merge(a1, a3, odd);
+        const unsigned l0 = lane_pair_merge(a2, a0, !odd), l1 = lane_pair_merge(a3, a1, !odd);
+        r4 = split_decode4(make_uint2(h0, h1), make_uint2(l0, l1));
       }
       v.x += r4.x; v.y += r4.y; v.z += r4.z; v.w += r4.w;
       }
       v = relu4(v);
       uint2 hp, lp;
-      encode4(v, hp, lp);
-      ovf |= hi_nonfinite_bits(hp);
-      const unsigned rx = lane_xor1((odd ? hp.x : lp.x)), ry = lane_xor1((odd ? hp.y : lp.y));
-      const uint4 stv = make_uint4(odd ? rx : hp.x, odd ? ry : hp.y, odd ? lp.x : rx, odd ? lp.y : ry);
+      split_encode4(v, hp, lp);
+      ovf |= split_hi_nonfinite_bits(hp);
+      const uint4 stv = split_pair_pack(hp, lp, odd);
       store_out_nt(outp + (int64_t)pr * C + col, stv);
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -879,8 +861,8 @@ __global__ __launch_bounds__(256, 2) void bottleneck_halves_kernel(Params p) {
         v = relu4(v);                                                                                                \
         if (!inside) v = make_float4(0.f, 0.f, 0.f, 0.f);                                                            \
         uint2 hi, lo;                                                                                                \
-        encode4(v, hi, lo);                                                                                          \
-        ovf |= hi_nonfinite_bits(hi);                                                                                \
+        split_encode4(v, hi, lo);                                                                                    \
+        ovf |= split_hi_nonfinite_bits(hi);                                                                          \
         unsigned char* d = smem + (hp0 + l32) * K::PYH + (ch >> 3) * 32 + h * 8;                                     \
         *reinterpret_cast<uint2*>(d) = hi; *reinterpret_cast<uint2*>(d + 16) = lo;                                   \
       }                                                                                                              \
@@ -925,8 +907,8 @@ __global__ __launch_bounds__(256, 2) void bottleneck_halves_kernel(Params p) {
       float4 v = make_float4(acc2[j][4 * q] * cs.x + bi.x, acc2[j][4 * q + 1] * cs.y + bi.y, acc2[j][4 * q + 2] * cs.z + bi.z, acc2[j][4 * q + 3] * cs.w + bi.w);
       v = relu4(v);
       uint2 hi, lo;
-      encode4(v, hi, lo);
-      ovf |= hi_nonfinite_bits(hi);
+      split_encode4(v, hi, lo);
+      ovf |= split_hi_nonfinite_bits(hi);
       unsigned char* d = patchb + l32 * K::P2 + q * 32 + h * 8;
       *reinterpret_cast<uint2*>(d) = hi; *reinterpret_cast<uint2*>(d + 16) = lo;
     }
@@ -1008,17 +990,16 @@ __global__ __launch_bounds__(256, 2) void bottleneck_halves_kernel(Params p) {
         float4 r4;
         {   // even lane holds hi0..7 of the 8-channel group, odd lane lo0..7; each needs hi and lo of ITS four channels
           const unsigned a0 = __float_as_uint(rw.x), a1 = __float_as_uint(rw.y), a2 = __float_as_uint(rw.z), a3 = __float_as_uint(rw.w);
-          const unsigned g0 = lane_xor1((odd ? a0 : a2)), g1 = lane_xor1((odd ? a1 : a3));
-          const unsigned h0 = odd ? g0 : a0, h1 = odd ? g1 : a1, l0 = odd ? a2 : g0, l1 = odd ? a3 : g1;
-          r4 = decode4(make_uint2(h0, h1), make_uint2(l0, l1));
+          const unsigned h0 = lane_pair_merge(a0, a2, odd), h1 = lane_pair_merge(a1, a3, odd);
+          const unsigned l0 = lane_pair_merge(a2, a0, !odd), l1 = lane_pair_merge(a3, a1, !odd);
+          r4 = split_decode4(make_uint2(h0, h1), make_uint2(l0, l1));
         }
         v.x += r4.x; v.y += r4.y; v.z += r4.z; v.w += r4.w;
         v = relu4(v);
         uint2 hp, lp;
-        encode4(v, hp, lp);
-        ovf |= hi_nonfinite_bits(hp);
-        const unsigned rx = lane_xor1((odd ? hp.x : lp.x)), ry = lane_xor1((odd ? hp.y : lp.y));
-        const uint4 stv = make_uint4(odd ? rx : hp.x, odd ? ry : hp.y, odd ? lp.x : rx, odd ? lp.y : ry);
+        split_encode4(v, hp, lp);
+        ovf |= split_hi_nonfinite_bits(hp);
+        const uint4 stv = split_pair_pack(hp, lp, odd);
         store_out_nt(outp + (int64_t)pr * C + col, stv);
       }
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");

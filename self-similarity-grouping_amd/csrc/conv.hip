@@ -39,25 +39,11 @@ typedef _Float16 v8h __attribute__((ext_vector_type(8)));
 // result is fp32-class (measured against fp64 next to the pure fp32 MFMA kernel in tests/test_gpu_parity.py)
 // at 3/16 of the fp32 MFMA cost.  Memory format ("h8l8"): per 8 consecutive channels 32 bytes =
 // [8 x half hi][8 x half lo] -- the same 4 bytes per value and the same addresses as the fp32 layout, so the
-// staging code below is shared by both element types.
+// staging code below is shared by both element types.  The codec itself (split_encode4, split_decode4, the range flag and the lane-pair
+// exchange of the epilogues) is in ssg_common.h, one copy for every kernel that produces or consumes the format.
+// two halves in one dword, the first in the low half (tests/test_host_exec.py compiles the text from this line to ConvParams for the host)
 __device__ __forceinline__ unsigned pack_h2(_Float16 a, _Float16 b) {
   return (unsigned)__builtin_bit_cast(unsigned short, a) | ((unsigned)__builtin_bit_cast(unsigned short, b) << 16);
-}
-__device__ __forceinline__ float unpack_lo(unsigned u) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(u & 0xffffu)); }
-__device__ __forceinline__ float unpack_hi(unsigned u) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(u >> 16)); }
-// 4 values -> (hi pair of dwords, lo pair of dwords)
-__device__ __forceinline__ void split_encode4(const float4 v, uint2& hi, uint2& lo) {
-  const _Float16 h0 = (_Float16)v.x, h1 = (_Float16)v.y, h2 = (_Float16)v.z, h3 = (_Float16)v.w;
-  hi = make_uint2(pack_h2(h0, h1), pack_h2(h2, h3));
-  lo = make_uint2(pack_h2((_Float16)(v.x - (float)h0), (_Float16)(v.y - (float)h1)), pack_h2((_Float16)(v.z - (float)h2), (_Float16)(v.w - (float)h3)));
-}
-// any of the four hi halves infinite or NaN (the value did not fit the split-half format)
-__device__ __forceinline__ bool split_hi_nonfinite(const uint2 hi) {
-  const unsigned a = hi.x & 0x7fff7fffu, b = hi.y & 0x7fff7fffu;
-  return (a & 0xffffu) >= 0x7c00u || (a >> 16) >= 0x7c00u || (b & 0xffffu) >= 0x7c00u || (b >> 16) >= 0x7c00u;
-}
-__device__ __forceinline__ float4 split_decode4(const uint2 hi, const uint2 lo) {
-  return make_float4(unpack_lo(hi.x) + unpack_lo(lo.x), unpack_hi(hi.x) + unpack_hi(lo.x), unpack_lo(hi.y) + unpack_lo(lo.y), unpack_hi(hi.y) + unpack_hi(lo.y));
 }
 
 struct ConvParams {
@@ -445,10 +431,7 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64, (BM / WM) * (BN / WN) =
           float4 r4 = rr[it];
           if (p.res_split) {
             // even lane holds hi0..7 of the 8-channel group, odd lane lo0..7; each needs hi and lo of ITS four channels
-            const unsigned s0 = odd ? __float_as_uint(r4.x) : __float_as_uint(r4.z), s1 = odd ? __float_as_uint(r4.y) : __float_as_uint(r4.w);
-            const unsigned g0 = lane_xor1(s0), g1 = lane_xor1(s1);
-            r4 = odd ? split_decode4(make_uint2(g0, g1), make_uint2(__float_as_uint(r4.z), __float_as_uint(r4.w)))
-                     : split_decode4(make_uint2(__float_as_uint(r4.x), __float_as_uint(r4.y)), make_uint2(g0, g1));
+            r4 = split_pair_decode4(__float_as_uint(r4.x), __float_as_uint(r4.y), __float_as_uint(r4.z), __float_as_uint(r4.w), odd);
           }
           v.x += r4.x; v.y += r4.y; v.z += r4.z; v.w += r4.w;
         }
@@ -457,9 +440,7 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64, (BM / WM) * (BN / WN) =
           uint2 hp, lp;
           split_encode4(v, hp, lp);
           if (p.overflow && split_hi_nonfinite(hp)) *p.overflow = 1;
-          const uint2 send = odd ? hp : lp;
-          const uint2 recv = make_uint2(lane_xor1(send.x), lane_xor1(send.y));
-          const uint4 st = odd ? make_uint4(recv.x, recv.y, lp.x, lp.y) : make_uint4(hp.x, hp.y, recv.x, recv.y);
+          const uint4 st = split_pair_pack(hp, lp, odd);
 #ifdef SSG_IGEMM_NT_STORE       // A/B knob: the register-staged kernel's split-half stores with the nt cache policy
           if (m < p.M) { const v4u sv_ = {st.x, st.y, st.z, st.w}; __builtin_nontemporal_store(sv_, reinterpret_cast<v4u*>(outp + (int64_t)m * p.Cout + col)); }
 #else
@@ -909,16 +890,15 @@ __global__ __launch_bounds__((BM / 64) * (BN / 64) * 64, BM == 256 ? 1 : (BN == 
             // even lane holds hi0..7 of the 8-channel group, odd lane lo0..7; each needs hi and lo of ITS four channels
             const unsigned a0 = rr[it][0], a1 = rr[it][1], a2 = rr[it][2], a3 = rr[it][3];
             if (n + 1 < NP) rr[it] = __builtin_amdgcn_raw_buffer_load_b128(res_rsrc, poff(n + 1, it), 0, SSG_DMA_RES_AUX);   // the next patch's piece, a whole patch ahead of its use
-            const unsigned g0 = lane_xor1(odd ? a0 : a2), g1 = lane_xor1(odd ? a1 : a3);
-            const float4 r4 = split_decode4(make_uint2(odd ? g0 : a0, odd ? g1 : a1), make_uint2(odd ? a2 : g0, odd ? a3 : g1));
+            const float4 r4 = split_pair_decode4(a0, a1, a2, a3, odd);
             v.x += r4.x; v.y += r4.y; v.z += r4.z; v.w += r4.w;
           }
           v.x = v.x > 0.f ? v.x : 0.f; v.y = v.y > 0.f ? v.y : 0.f; v.z = v.z > 0.f ? v.z : 0.f; v.w = v.w > 0.f ? v.w : 0.f;
           uint2 hp, lp;
           split_encode4(v, hp, lp);
-          ovf |= ((hp.x & 0x7c007c00u) + 0x04000400u) | ((hp.y & 0x7c007c00u) + 0x04000400u);   // bits 15 / 31: a hi half with an all-ones exponent
-          const unsigned rx = lane_xor1(odd ? hp.x : lp.x), ry = lane_xor1(odd ? hp.y : lp.y);
-          const v4u stv = {odd ? rx : hp.x, odd ? ry : hp.y, odd ? lp.x : rx, odd ? lp.y : ry};
+          ovf |= split_hi_nonfinite_bits(hp);   // bits 15 / 31: a hi half with an all-ones exponent
+          const uint4 st4 = split_pair_pack(hp, lp, odd);
+          const v4u stv = {st4.x, st4.y, st4.z, st4.w};
           __builtin_amdgcn_raw_buffer_store_b128(stv, out_rsrc, poff(n, it), 0, RES ? SSG_DMA_OUT_AUX_RES : SSG_DMA_OUT_AUX);
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -958,10 +938,7 @@ __global__ __launch_bounds__((BM / 64) * (BN / 64) * 64, BM == 256 ? 1 : (BN == 
         if (resp) {
           float4 r4 = rr[it];
           if (p.res_split) {
-            const unsigned s0 = odd ? __float_as_uint(r4.x) : __float_as_uint(r4.z), s1 = odd ? __float_as_uint(r4.y) : __float_as_uint(r4.w);
-            const unsigned g0 = lane_xor1(s0), g1 = lane_xor1(s1);
-            r4 = odd ? split_decode4(make_uint2(g0, g1), make_uint2(__float_as_uint(r4.z), __float_as_uint(r4.w)))
-                     : split_decode4(make_uint2(__float_as_uint(r4.x), __float_as_uint(r4.y)), make_uint2(g0, g1));
+            r4 = split_pair_decode4(__float_as_uint(r4.x), __float_as_uint(r4.y), __float_as_uint(r4.z), __float_as_uint(r4.w), odd);
           }
           v.x += r4.x; v.y += r4.y; v.z += r4.z; v.w += r4.w;
         }
@@ -970,9 +947,7 @@ __global__ __launch_bounds__((BM / 64) * (BN / 64) * 64, BM == 256 ? 1 : (BN == 
           uint2 hp, lp;
           split_encode4(v, hp, lp);
           if (p.overflow && split_hi_nonfinite(hp)) *p.overflow = 1;
-          const uint2 send = odd ? hp : lp;
-          const uint2 recv = make_uint2(lane_xor1(send.x), lane_xor1(send.y));
-          const uint4 stv = odd ? make_uint4(recv.x, recv.y, lp.x, lp.y) : make_uint4(hp.x, hp.y, recv.x, recv.y);
+          const uint4 stv = split_pair_pack(hp, lp, odd);
           if (m < p.M) *reinterpret_cast<uint4*>(outp + (int64_t)m * p.Cout + col) = stv;
         } else if (m < p.M) *reinterpret_cast<float4*>(outp + (int64_t)m * p.Cout + col) = v;
       }

@@ -33,19 +33,7 @@ constexpr int CPITCH = 272;                          // conv tile: 192 pixels x 
 constexpr int CONV_BYTES = 3 * OW * CPITCH;
 constexpr int KSTEPS = 14, KROW = 224;               // 56 tap slots of 4 fp32-sized containers per weight row
 
-__device__ __forceinline__ unsigned pk2(_Float16 a, _Float16 b) {
-  return (unsigned)__builtin_bit_cast(unsigned short, a) | ((unsigned)__builtin_bit_cast(unsigned short, b) << 16);
-}
-__device__ __forceinline__ void enc4(const float4 v, uint2& hi, uint2& lo) {
-  const _Float16 h0 = (_Float16)v.x, h1 = (_Float16)v.y, h2 = (_Float16)v.z, h3 = (_Float16)v.w;
-  hi = make_uint2(pk2(h0, h1), pk2(h2, h3));
-  lo = make_uint2(pk2((_Float16)(v.x - (float)h0), (_Float16)(v.y - (float)h1)), pk2((_Float16)(v.z - (float)h2), (_Float16)(v.w - (float)h3)));
-}
-__device__ __forceinline__ float flo(unsigned u) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(u & 0xffffu)); }
-__device__ __forceinline__ float fhi(unsigned u) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(u >> 16)); }
-__device__ __forceinline__ float4 dec4(const uint2 hi, const uint2 lo) {
-  return make_float4(flo(hi.x) + flo(lo.x), fhi(hi.x) + fhi(lo.x), flo(hi.y) + flo(lo.y), fhi(hi.y) + fhi(lo.y));
-}
+// (the split-half codec is ssg_common.h's: split_encode4, split_decode4, split_hi_nonfinite_bits)
 
 #ifdef SSG_STEM_PROF
 __device__ unsigned long long g_stem_prof[8];           // ticks per phase, summed over workgroups (thread 0)
@@ -73,7 +61,7 @@ __device__ __forceinline__ void store_item(unsigned char* dst, const Item& it, i
   for (int k = 0; k < 4; k++) {
     const int s = flip ? 3 - k : k;
     uint2 hi, lo;
-    enc4(make_float4(rr[s], gg[s], bb[s], 0.f), hi, lo);
+    split_encode4(make_float4(rr[s], gg[s], bb[s], 0.f), hi, lo);
     *reinterpret_cast<uint4*>(dst + k * 16) = it.inside ? make_uint4(hi.x, hi.y, lo.x, lo.y) : make_uint4(0u, 0u, 0u, 0u);
   }
 }
@@ -117,9 +105,9 @@ __device__ __forceinline__ unsigned tile_to_lds(const v16f& acc, const float* cs
     float4 v = make_float4(acc[4 * q] * c4.x + b4.x, acc[4 * q + 1] * c4.y + b4.y, acc[4 * q + 2] * c4.z + b4.z, acc[4 * q + 3] * c4.w + b4.w);
     v = make_float4(v.x > 0.f ? v.x : 0.f, v.y > 0.f ? v.y : 0.f, v.z > 0.f ? v.z : 0.f, v.w > 0.f ? v.w : 0.f);
     uint2 hi, lo;
-    enc4(v, hi, lo);
-    ovf |= ((hi.x & 0x7c007c00u) + 0x04000400u) | ((hi.y & 0x7c007c00u) + 0x04000400u);
-    *reinterpret_cast<float4*>(dst_pixel + ch * 4) = dec4(hi, lo);
+    split_encode4(v, hi, lo);
+    ovf |= split_hi_nonfinite_bits(hi);
+    *reinterpret_cast<float4*>(dst_pixel + ch * 4) = split_decode4(hi, lo);
   }
   return ovf;
 }
@@ -224,7 +212,7 @@ __global__ __launch_bounds__(256, 2) void stem_pool_kernel(const float* __restri
       }
     }
     uint2 ha, la, hb, lb;
-    enc4(m0, ha, la); enc4(m1, hb, lb);
+    split_encode4(m0, ha, la); split_encode4(m1, hb, lb);
     float* o = out + ((((int64_t)b * OHP + pr) * PW + pp) * 64 + cg * 8);
     *reinterpret_cast<uint4*>(o) = make_uint4(ha.x, ha.y, hb.x, hb.y);
     *reinterpret_cast<uint4*>(o + 4) = make_uint4(la.x, la.y, lb.x, lb.y);
